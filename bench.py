@@ -11,9 +11,17 @@ add_noise, UNet forward) -> lm_head + CE -> loss = 10*vm + 1*lm -> backward (LLM
 all-reduce through DDP when N > 1] -> global-norm clip + AdamW.  Nothing is skipped inside the timed region.
 
 value = whole-job training samples (sequences)/s = N*16*K / max-over-ranks wall time.  Weak scaling (16 seq/GPU).
-Also reported in the same JSON line (not part of `value`): SD-2.1 512 px denoise steps/s (50 deterministic DDIM steps,
+
+A plain run does only what `value` needs: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs), the JSON
+line.  `--full` adds, in the same JSON line (not part of `value`): SD-2.1 512 px denoise steps/s (50 deterministic DDIM steps,
 CFG 7.5 => UNet batch 2*B_img per step), `roofline` for the dominant kernel (the bf16 MFMA GEMM family, timed per launch
-with HIP events on the launch stream), `cpu_baseline` (oracle decoder layer fwd+bwd on the host cores, rank 0, N=1 only).
+with HIP events on the launch stream, warm-up and timed steps), the ragged and gradient-checkpointing training legs, the
+other BASELINE.json configs, and `cpu_baseline` (oracle decoder layer fwd+bwd on the host cores, rank 0, N=1 only).
+
+--dump-outputs DIR writes what the last timed step handed its caller, as float32 / float64 .npy files (rank 0): the losses
+and the global gradient norm of that step, and the trainable parameters after it plus their update over the K timed steps,
+both at a fixed seeded sample of 4096 elements per tensor.  Weights, batch and draws are seeded: the same arguments give
+the same inputs on every run.
 """
 import argparse
 import json
@@ -60,7 +68,15 @@ def parse():
     ap.add_argument("--launch-check", action="store_true",
                     help="launcher dry run: form the N-rank process group, all-reduce a one per rank, print one JSON line, exit "
                          "(no GPU work; with --backend gloo it runs on CPU: tests/test_distributed_cpu.py)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: denoise legs, GEMM roofline, ragged and gradient-checkpointing "
+                         "legs, configs 2 / 5, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed training step to DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.dump_outputs and a.no_train:
+        ap.error("--dump-outputs writes the training step's outputs: it cannot go with --no-train")
+    return a
 
 
 def self_launch(a):
@@ -203,6 +219,34 @@ def cpu_baseline(seq_len, budget_s=60.0):
                        f"VAE not included; host has {os.cpu_count()} logical cores")
 
 
+DUMP_PER_TENSOR = 4096
+DUMP_MAX_BYTES = 64 << 20
+
+
+def param_sample_index(params, seed=0):
+    """Fixed, seeded positions (DUMP_PER_TENSOR per tensor, drawn with replacement) into each flattened parameter."""
+    g = torch.Generator().manual_seed(seed)
+    return [torch.randint(0, p.numel(), (DUMP_PER_TENSOR,), generator=g).to(p.device) for p in params]
+
+
+def param_sample(params, index):
+    """[n_tensors, DUMP_PER_TENSOR] fp32 values of the parameters at `index` (stays on the device)."""
+    return torch.stack([p.detach().reshape(-1)[i].float() for p, i in zip(params, index)])
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy (float32 or float64), at most DUMP_MAX_BYTES in all."""
+    import numpy as np
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -255,7 +299,7 @@ def main():
 
     # ------------------------------------------------------------------ M2: SD-2.1 512 px denoise steps/s (replicas)
     denoise = None
-    if not a.no_denoise:
+    if a.full and not a.no_denoise:
         nq = model.model.dream_embedding.embed_len
         legs = []
         for Bi in ([a.denoise_batch] if a.denoise_batch != 1 else ([1] if (tiny or world > 1) else [1, 8])):  # B_img in {1, 8}
@@ -328,17 +372,21 @@ def main():
         if world > 1 and a.warmup < 1:
             step()   # torch DDP (static_graph) uses ONE all-gradient bucket in its first two iterations and the rebuilt 512 MB buckets
                      # from the third (tools/ddp_dry_7b.py): the timed region must never contain one of those two
-        # warm-up steps run with the per-launch HIP-event timing switched on as well, so that the timed region starts in
-        # steady state; the events the timed region will need are created here, outside it
-        ops.GEMM_PROFILE = []
+        # --full: warm-up steps run with the per-launch HIP-event timing switched on as well, so that the timed region starts in
+        # steady state; the events the timed region will need are created here, outside it.  A plain run times the bare step.
+        ops.GEMM_PROFILE = [] if a.full else None
         for _ in range(a.warmup):
             out = step()
-        per_step = (len(ops.GEMM_PROFILE) // a.warmup) if a.warmup > 0 else 1400
-        ops.GEMM_PROFILE = None
-        ops.prealloc_gemm_events(2 * per_step * a.steps + 64)
+        if a.full:
+            per_step = (len(ops.GEMM_PROFILE) // a.warmup) if a.warmup > 0 else 1400
+            ops.GEMM_PROFILE = None
+            ops.prealloc_gemm_events(2 * per_step * a.steps + 64)
+        if a.dump_outputs and rank == 0:
+            dump_index = param_sample_index(params)
+            dump_before = param_sample(params, dump_index)
         D.synchronize()
         torch.cuda.synchronize()
-        ops.GEMM_PROFILE = []
+        ops.GEMM_PROFILE = [] if a.full else None
         if timeline is not None:
             per_step_buckets = max(1, len(timeline.records) // max(1, a.warmup + 1))
             timeline.reset()
@@ -353,21 +401,24 @@ def main():
         comm = timeline.summary() if timeline is not None else None
         prof, ops.GEMM_PROFILE = ops.GEMM_PROFILE, None
         loss_val = float(out.loss.item())
-        gsum = sum(f for _, _, f, _ in prof)
-        tsum = sum(s.elapsed_time(e) for s, e, _, _ in prof) * 1e-3
-        by_tag = {}
-        for s, e, f, tag in prof:
-            d = by_tag.setdefault(tag, [0.0, 0.0, 0])
-            d[0] += f
-            d[1] += s.elapsed_time(e) * 1e-3
-            d[2] += 1
+        if a.dump_outputs and rank == 0:
+            after = param_sample(params, dump_index)
+            info = out.additional_log_info
+            gnorm = getattr(opt, "last_grad_norm", None)
+            dump_outputs(a.dump_outputs, dict(
+                loss=out.loss.detach().double().cpu().numpy(),
+                lm_loss=torch.as_tensor(info["lm_loss"]).detach().double().cpu().numpy(),
+                vm_loss=torch.as_tensor(info["vm_loss"]).detach().double().cpu().numpy(),
+                **({} if gnorm is None else {"grad_norm": gnorm.detach().double().cpu().numpy()}),
+                params_sample=after.cpu().numpy(),
+                params_update_sample=(after - dump_before).cpu().numpy()))
+            del after, dump_before, dump_index
         samples = world * a.batch * a.steps
         value = samples / dt
         # share of the S rows of a sample that carry an LM label (after the shift): what the fused lm_head + CE unit runs on
         lab = batch.get("labels")
         lab_share = float((lab[:, 1:] != -100).sum().item()) / float(lab.shape[0] * lab.shape[1]) if torch.is_tensor(lab) else 1.0
         flops_required = FLOPS_TRAIN_SAMPLE - 3 * FLOPS_LM_HEAD_TOKEN * a.seq_len * (1.0 - lab_share)
-        achieved = gsum / tsum / 1e12 if tsum > 0 else 0.0
         # HBM-side bytes of one launch of the dominant shape, from separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes
         # (profiles/roofline_traffic.json; corrected as MI355X_MICROARCH.md prescribes).  A number, per launch, like `achieved`.
         traffic, traffic_detail = None, None
@@ -383,15 +434,27 @@ def main():
                                             "L2->fabric requests, mostly Infinity-Cache hits)"}
             except Exception:
                 traffic, traffic_detail = None, None
+        roofline = None
+        if a.full:
+            gsum = sum(f for _, _, f, _ in prof)
+            tsum = sum(s.elapsed_time(e) for s, e, _, _ in prof) * 1e-3
+            by_tag = {}
+            for s, e, f, tag in prof:
+                d = by_tag.setdefault(tag, [0.0, 0.0, 0])
+                d[0] += f
+                d[1] += s.elapsed_time(e) * 1e-3
+                d[2] += 1
+            achieved = gsum / tsum / 1e12 if tsum > 0 else 0.0
+            roofline = dict(bound="mfma", kernel="bf16 MFMA GEMM family: gemm_w4m_kernel (the decoder's linears) / gemm_pipe_kernel / gemm_pipe_tail_kernel / gemm_ring_kernel / gemm_bf16_kernel (linear fwd/dgrad/wgrad + implicit-GEMM conv)",
+                            achieved=round(achieved, 1), peak=PEAK_BF16_TFLOPS, unit="TFLOP/s", frac=round(achieved / PEAK_BF16_TFLOPS, 4),
+                            traffic=traffic, traffic_measured=False, traffic_detail=traffic_detail, launches_per_step=len(prof) // max(a.steps, 1),
+                            avg_launch_ms=round(1e3 * tsum / max(len(prof), 1), 4),
+                            time_share_of_step=round(tsum / dt, 4),
+                            by_kind={k: dict(tflops=round(v[0] / v[1] / 1e12, 1), launches=v[2] // max(a.steps, 1))
+                                     for k, v in by_tag.items() if v[1] > 0})
         train = dict(
             value=value, ms_per_step=1e3 * dt / a.steps, loss=loss_val,
-            roofline=dict(bound="mfma", kernel="bf16 MFMA GEMM family: gemm_w4m_kernel (the decoder's linears) / gemm_pipe_kernel / gemm_pipe_tail_kernel / gemm_ring_kernel / gemm_bf16_kernel (linear fwd/dgrad/wgrad + implicit-GEMM conv)",
-                          achieved=round(achieved, 1), peak=PEAK_BF16_TFLOPS, unit="TFLOP/s", frac=round(achieved / PEAK_BF16_TFLOPS, 4),
-                          traffic=traffic, traffic_measured=False, traffic_detail=traffic_detail, launches_per_step=len(prof) // max(a.steps, 1),
-                          avg_launch_ms=round(1e3 * tsum / max(len(prof), 1), 4),
-                          time_share_of_step=round(tsum / dt, 4),
-                          by_kind={k: dict(tflops=round(v[0] / v[1] / 1e12, 1), launches=v[2] // max(a.steps, 1))
-                                   for k, v in by_tag.items() if v[1] > 0}),
+            roofline=roofline,
             # SURVEY §8(d)'s 88.1 TFLOP / sample counts lm_head fwd + bwd on all S rows; the step computes it on the labelled rows only
             # (the rest of an interleaved document carries no LM loss): the headline fraction uses the FLOPs the step REQUIRES
             e2e_frac_mfma_peak=None if tiny else round(value / world * flops_required / (PEAK_BF16_TFLOPS * 1e12), 4),
@@ -407,7 +470,7 @@ def main():
     # alone on the padded grid -- modeling_dreamllm._token_pack; DREAMLLM_PACK_RAGGED=0 restores the padded-grid GEMMs of the reference).
     # Same model / optimizer state; 1 warm-up + `--ragged-steps` timed steps.
     ragged = None
-    if not a.no_train and not a.no_ragged and not tiny and world == 1:   # N = 1 only: a rank that fails alone inside this try
+    if a.full and not a.no_train and not a.no_ragged and not tiny and world == 1:   # N = 1 only: a rank that fails alone inside this try
         try:                                                                  # would leave the others in a collective
             rb = make_interleaved_batch(a.batch, a.seq_len, a.images_per_sample, seed=4321 + rank, device=dev, ragged=True)
             lens = rb["attention_mask"].sum(1).tolist()
@@ -455,7 +518,7 @@ def main():
     # Not the headline (288 GB hold the 7B activations: recompute only costs time here); reported so that both modes have a measured
     # step time and peak.  Same model / optimizer / batch; 1 warm-up + 2 timed steps.
     grad_ckpt = None
-    if not a.no_train and not a.no_grad_ckpt_leg and not tiny and world == 1:
+    if a.full and not a.no_train and not a.no_grad_ckpt_leg and not tiny and world == 1:
         try:
             model.gradient_checkpointing_enable()
             step()
@@ -477,7 +540,7 @@ def main():
 
     # ------------------------------------------------------------------ the other BASELINE.json configs (N = 1 only, short)
     configs = None
-    if world == 1 and not tiny and not a.no_configs:
+    if a.full and world == 1 and not tiny and not a.no_configs:
         configs = {}
         try:
             del batch, opt, ddp
@@ -529,7 +592,7 @@ def main():
             "denoise": denoise,
             "configs": configs,
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(a.seq_len)
             except Exception as ex:  # the baseline is informational; never lose the GPU line

@@ -8,7 +8,7 @@ cd $ROOT
 python -m pytest tests -q -m gpu 2>&1 | tail -12 > $OUT/r05_gpu_tests.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 >> $OUT/r05_gpu_tests.log
 cp $OUT/parity_report.json $OUT/r05_parity_report.json 2>/dev/null
-python bench.py --steps 10 --warmup 2 > $OUT/r05_bench_final.log 2> $OUT/r05_bench_final.err
+python bench.py --full --steps 10 --warmup 2 > $OUT/r05_bench_final.log 2> $OUT/r05_bench_final.err
 python tools/attn_bench.py 2>&1 | grep -v amdgpu.ids > $OUT/r05_attn_bench.log
 python tools/attn_bwd_pp_timeline.py 2>&1 | grep -v amdgpu.ids > $OUT/r05_attn_bwd_pp_timeline.log
 python tools/attn_bwd_ab.py 2>&1 | grep " ms" > $OUT/r05_attn_bwd_ab.log

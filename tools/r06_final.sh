@@ -10,7 +10,7 @@ if [ "$1" != "profiles-only" ]; then
   python -m pytest tests -q -m gpu 2>&1 | tail -12 > $OUT/r06_gpu_tests.log
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 >> $OUT/r06_gpu_tests.log
   cp $ROOT/gpurun_out/parity_report.json $OUT/r06_parity_report.json 2>/dev/null
-  python bench.py --steps 10 --warmup 2 > $OUT/r06_bench_final.log 2> $OUT/r06_bench_final.err
+  python bench.py --full --steps 10 --warmup 2 > $OUT/r06_bench_final.log 2> $OUT/r06_bench_final.err
   python tools/attn_bench.py 2>&1 | grep -v amdgpu.ids > $OUT/r06_attn_bench.log
 fi
 cd /tmp && export TMPDIR=/tmp
