@@ -126,15 +126,30 @@ class GreedyDecodeSession:
         else:
             hf, _, _ = ops.rmsnorm_fwd(x, m.model.norm.weight, eps)
             logits = ops.gemv(hf, m.lm_head.weight, out_dtype=torch.float32)
+        self._choose(logits)
+        self.pos.add_(1)
+        self.kv_len.add_(1)
+        self.slot.add_(1)
+        return logits
+
+    def _choose(self, logits):
+        """Token choice of a step (inside the captured graph): writes `tok` and `out_tokens[step]`, advances the step."""
         nxt = logits[:, : self.vocab_limit].argmax(-1)
         nxt = torch.where(self.force_mask.index_select(0, self.step_idx)[0], self.force_tok.index_select(0, self.step_idx)[0], nxt)
         self.out_tokens.index_copy_(0, self.step_idx, nxt[None])
         self.tok.copy_(nxt)
-        self.pos.add_(1)
-        self.kv_len.add_(1)
-        self.slot.add_(1)
         self.step_idx.add_(1)
-        return logits
+
+    def _choose_first(self, logits, forced_tok, forced_mask):
+        """First token after the prompt from the prefill's last-position logits [B, V]; forced_tok / forced_mask [B] or None."""
+        first = logits[:, : self.vocab_limit].argmax(-1)
+        if forced_tok is not None:
+            first = torch.where(forced_mask, forced_tok, first)
+        return first
+
+    def _state(self):
+        """Device state a token step changes (saved around the warm-up step before capture)."""
+        return (self.tok, self.pos, self.kv_len, self.slot, self.step_idx, self.out_tokens)
 
     # ---- public ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -170,14 +185,16 @@ class GreedyDecodeSession:
         for li, (k, v) in enumerate(out.past_key_values):  # reference layout [B, Hkv, S, D]
             self.kc[li][:, :S].copy_(k.transpose(1, 2))
             self.vc[li][:, :S].copy_(v.transpose(1, 2))
-        first = out.logits[:, -1, : self.vocab_limit].argmax(-1)
         self.force_mask.zero_()
+        f_tok = f_mask = None
         if forced_tokens is not None:
             n = forced_tokens.shape[1]
             if n > 0:
-                first = torch.where(forced_mask[:, 0].to(dev), forced_tokens[:, 0].to(dev), first)
+                f_tok, f_mask = forced_tokens[:, 0].to(dev), forced_mask[:, 0].to(dev)
                 self.force_tok[: n - 1].copy_(forced_tokens[:, 1:].t())
                 self.force_mask[: n - 1].copy_(forced_mask[:, 1:].t())
+        self.step_idx.zero_()
+        first = self._choose_first(out.logits[:, -1], f_tok, f_mask)
         self.tok.copy_(first)
         if lens is None:
             self.pos.fill_(S)
@@ -185,7 +202,6 @@ class GreedyDecodeSession:
             self.pos.copy_(lens[:, None])
         self.kv_len.fill_(S + 1)
         self.slot.copy_(torch.arange(B, device=dev) * self.max_len + S)
-        self.step_idx.zero_()
         self.prompt_len = S
         self.generated = 0  # tokens produced by generate() since this prefill (host-side count of graph replays)
         self.first = first
@@ -199,18 +215,18 @@ class GreedyDecodeSession:
         if n_more <= 0:
             return self.out_tokens[:0].t()
         if self.use_graph and self.graph is None:
-            state = [t.clone() for t in (self.tok, self.pos, self.kv_len, self.slot, self.step_idx, self.out_tokens)]
+            state = [t.clone() for t in self._state()]
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):  # warm-up outside capture
                 self._token_step()
             torch.cuda.current_stream().wait_stream(side)
-            for t, s in zip((self.tok, self.pos, self.kv_len, self.slot, self.step_idx, self.out_tokens), state):
+            for t, s in zip(self._state(), state):
                 t.copy_(s)  # the warm-up wrote cache row `slot`, which the first real step rewrites identically
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self.logits = self._token_step()
-            for t, s in zip((self.tok, self.pos, self.kv_len, self.slot, self.step_idx, self.out_tokens), state):
+            for t, s in zip(self._state(), state):
                 t.copy_(s)  # capture does not execute, but keep the state explicit
         for _ in range(n_more):
             if self.use_graph:
@@ -220,3 +236,69 @@ class GreedyDecodeSession:
         start = self.generated
         self.generated += n_more
         return self.out_tokens[start:start + n_more].t().contiguous()
+
+
+class SampledDecodeSession(GreedyDecodeSession):
+    """`GreedyDecodeSession` whose token choice samples (`ops.sample_logits`, csrc/sample.hip): temperature, top-k, top-p, the draw,
+    teacher forcing, HF's finished-row rule and the step counter in ONE launch inside the captured graph, in place of the greedy
+    step's argmax + bookkeeping launches.
+
+    u comes from Philox4x32-10 keyed by the seed given to `prefill` (a device buffer) at counter (row, step): the prefill's token is
+    step 0 and graph replay i is step i + 1.  With `eos` >= 0 a row that has emitted eos emits `pad` from then on (`finished`, a
+    device buffer, reset by `prefill`)."""
+
+    def __init__(self, model, batch_size: int, max_len: int, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                 eos: int | None = None, pad: int = 0, fixed_u: float | None = None, **kw):
+        super().__init__(model, batch_size, max_len, **kw)
+        if not temperature > 0:
+            raise ValueError("SampledDecodeSession: temperature must be > 0 (use GreedyDecodeSession for temperature 0)")
+        if self.vocab_limit > 32768:
+            raise ValueError("SampledDecodeSession: the sampling kernel covers at most 32768 ids")
+        dev = self.tok.device
+        self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
+        self.eos, self.pad = (-1 if eos is None else int(eos)), int(pad)
+        # the kernel indexes [step][b] with step 0 = the prefill's token: row 0 of these buffers belongs to it, rows 1.. are the
+        # greedy session's out_tokens / force_tok / force_mask (views, so the inherited prefill / generate index them unchanged)
+        self._out_all = torch.zeros(max_len + 1, batch_size, dtype=torch.long, device=dev)
+        self._ftok_all = torch.zeros(max_len + 1, batch_size, dtype=torch.long, device=dev)
+        self._fmask_all = torch.zeros(max_len + 1, batch_size, dtype=torch.bool, device=dev)
+        self.out_tokens, self.force_tok, self.force_mask = self._out_all[1:], self._ftok_all[1:], self._fmask_all[1:]
+        self.seed = torch.zeros(1, dtype=torch.long, device=dev)
+        self.rng_step = torch.zeros(1, dtype=torch.long, device=dev)
+        self.arrive = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.finished = torch.zeros(batch_size, dtype=torch.bool, device=dev)
+        self.status = torch.zeros(batch_size, dtype=torch.int32, device=dev)
+        # fixed_u: every draw uses this u instead of the Philox stream (0 with top-k 1 = greedy search)
+        self.uniforms = None if fixed_u is None else torch.full((batch_size,), float(fixed_u), dtype=torch.float32, device=dev)
+
+    def _sample(self, logits):
+        ops.sample_logits(logits, self.temperature, self.top_k, self.top_p, vocab_limit=self.vocab_limit, seed=self.seed,
+                          step=self.rng_step, out_tokens=self._out_all, force_tok=self._ftok_all, force_mask=self._fmask_all,
+                          eos=self.eos, pad=self.pad, finished=self.finished, tok_out=self.tok, status=self.status,
+                          advance_step=True, arrive=self.arrive, uniforms=self.uniforms)
+
+    def _choose(self, logits):
+        self._sample(logits)
+
+    def _choose_first(self, logits, forced_tok, forced_mask):
+        if forced_tok is not None:
+            self._ftok_all[0].copy_(forced_tok)
+            self._fmask_all[0].copy_(forced_mask)
+        else:
+            self._fmask_all[0].zero_()
+        self.rng_step.zero_()
+        self.finished.zero_()
+        self.status.zero_()
+        self.first_logits = logits.float()
+        self._sample(self.first_logits)
+        return self._out_all[0].clone()
+
+    def _state(self):
+        return super()._state() + (self.rng_step, self.finished, self.status)
+
+    @torch.no_grad()
+    def prefill(self, input_ids, images=None, attention_mask=None, forced_tokens=None, forced_mask=None, seed: int = 0):
+        """`GreedyDecodeSession.prefill` with the first token sampled; `seed` (int64) keys every draw until the next prefill."""
+        self.seed.fill_(int(seed))
+        return super().prefill(input_ids, images=images, attention_mask=attention_mask, forced_tokens=forced_tokens,
+                               forced_mask=forced_mask)

@@ -1327,6 +1327,215 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
             return tokens
         return torch.cat([input_ids, new], dim=1)
 
+    # transformers 4.35.2 GenerationConfig arguments `generate` does not implement, with the default value they may be passed at
+    _GENERATE_UNSUPPORTED = {"num_beams": 1, "num_return_sequences": 1, "repetition_penalty": 1.0, "typical_p": 1.0,
+                             "output_scores": False, "return_dict_in_generate": False, "output_attentions": False,
+                             "output_hidden_states": False, "num_beam_groups": 1, "diversity_penalty": 0.0, "penalty_alpha": None,
+                             "no_repeat_ngram_size": 0, "length_penalty": 1.0, "early_stopping": False, "bad_words_ids": None,
+                             "force_words_ids": None, "constraints": None, "logits_processor": None, "prefix_allowed_tokens_fn": None,
+                             "min_length": 0, "min_new_tokens": None, "epsilon_cutoff": 0.0, "eta_cutoff": 0.0,
+                             "encoder_repetition_penalty": 1.0, "renormalize_logits": False, "forced_bos_token_id": None,
+                             "forced_eos_token_id": None, "suppress_tokens": None, "begin_suppress_tokens": None,
+                             "sequence_bias": None, "guidance_scale": None, "exponential_decay_length_penalty": None,
+                             "assistant_model": None, "streamer": None, "generation_config": None, "negative_prompt_ids": None}
+    _GENERATE_IGNORED = ("use_cache", "synced_gpus")  # always a KV cache; one process per sequence batch
+
+    @staticmethod
+    def _draw_seed(generator):
+        """One int64 per call from `generator` or torch's default CPU generator (so `torch.manual_seed` makes a call reproducible)."""
+        return int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), generator=generator, dtype=torch.int64).item())
+
+    @torch.no_grad()
+    def sample_generate(self, input_ids, max_new_tokens, temperature=0.8, top_p=0.95, top_k=0, images=None, attention_mask=None,
+                        pad_token_id=None, vocab_limit="auto", generator=None, fast=None, use_graph=True):
+        """Sampled decode with a KV cache: the loop of omni/eval/language_eval/modeling_dreamllm.py:47-109 with temperature > 0
+        (`sample_top_p`, :36-43,86-91; defaults T 0.8, top-p 0.95), optionally top-k first (HF order: temperature, top-k, top-p).
+        Same three protocols, return layouts, `vocab_limit` and `fast` / `use_graph` as `greedy_generate`; `temperature == 0` IS
+        `greedy_generate` (bit-identical).  The token choice is one HIP launch per step (`dllm_sample_logits`) inside the captured
+        graph.  u comes from Philox4x32-10 keyed by one int64 drawn from `generator` (or torch's default CPU generator) per call:
+        `torch.manual_seed(s)` makes a call reproducible, but the stream is NOT the one `torch.multinomial` would draw."""
+        if temperature == 0:
+            return self.greedy_generate(input_ids, max_new_tokens, images=images, fast=fast, use_graph=use_graph,
+                                        attention_mask=attention_mask, pad_token_id=pad_token_id, vocab_limit=vocab_limit)
+        if vocab_limit == "auto":
+            vocab_limit = None if attention_mask is not None else 32000
+        return self._sampled_decode(input_ids, max_new_tokens, float(temperature), int(top_k), float(top_p), vocab_limit, images,
+                                    attention_mask, pad_token_id, self._draw_seed(generator), fast, use_graph)[0]
+
+    def _sampled_decode(self, input_ids, max_new_tokens, temperature, top_k, top_p, vocab_limit, images, attention_mask,
+                        pad_token_id, seed, fast, use_graph, eos=None, pad=0, stopping_criteria=None, greedy=False):
+        """Shared body of `sample_generate` / `generate`.  Returns (tokens, number of new tokens before the trim).  `greedy`: u = 0
+        for every draw (with top-k 1: the first arg-max, as argmax picks it)."""
+        B, S = input_ids.shape
+        dev = input_ids.device
+        V = min(int(vocab_limit), self.config.vocab_size) if vocab_limit is not None else self.config.vocab_size
+        if fast is None:
+            fast = B <= 8
+        tokens = forced = fm = None
+        if pad_token_id is not None:
+            if attention_mask is not None:
+                raise ValueError("pass either pad_token_id (right-padded ragged prompts) or attention_mask (left-padded), not both")
+            text_mask = input_ids != pad_token_id
+            plen = text_mask.sum(-1)
+            if not bool((text_mask == (torch.arange(S, device=dev)[None] < plen[:, None])).all()):
+                raise ValueError("pad_token_id protocol: prompts must be right-padded")
+            s0 = int(plen.min())
+            total = S + max_new_tokens
+            tokens = torch.full((B, total), pad_token_id, dtype=torch.long, device=dev)
+            tokens[:, :S] = input_ids
+            fmask = torch.zeros(B, total, dtype=torch.bool, device=dev)
+            fmask[:, :S] = text_mask
+            forced, fm = tokens[:, s0:], fmask[:, s0:]
+            n_new = total - s0
+            prompt = input_ids[:, :s0]
+        else:
+            prompt, n_new = input_ids, max_new_tokens
+        eos = -1 if eos is None else int(eos)
+        crit = list(stopping_criteria or [])
+
+        def stop_after(new_so_far, scores):
+            ids = torch.cat([input_ids, new_so_far], 1)
+            for c in crit:
+                r = c(ids, scores)
+                if bool(r.all()) if isinstance(r, torch.Tensor) else bool(r):
+                    return True
+            return False
+
+        done = n_new
+        if fast:
+            from .decode import SampledDecodeSession
+            key = ("sample", B, prompt.shape[1] + n_new + 1, use_graph, V, temperature, top_k, top_p, eos, int(pad), greedy)
+            sess = getattr(self, "_decode_session", None)
+            if sess is None or sess[0] != key:
+                sess = (key, SampledDecodeSession(self, B, key[2], temperature, top_k, top_p, eos=eos, pad=pad, use_graph=use_graph,
+                                                  vocab_limit=V, fixed_u=0.0 if greedy else None))
+                self._decode_session = sess
+            sess = sess[1]
+            first = sess.prefill(prompt, images=images, attention_mask=attention_mask, forced_tokens=forced, forced_mask=fm, seed=seed)
+            parts = [first[:, None]]
+            n = 1
+            if crit and stop_after(first[:, None], sess.first_logits):
+                done = 1
+            elif eos >= 0 and bool(sess.finished.all()):
+                done = 1
+            else:
+                while n < n_new:
+                    m = 1 if crit else min(16, n_new - n)  # criteria see every token; eos alone is checked between chunks
+                    parts.append(sess.generate(m))
+                    n += m
+                    if crit and stop_after(torch.cat(parts, 1), sess.logits):
+                        done = n
+                        break
+                    if eos >= 0 and bool(sess.finished.all()):
+                        new = torch.cat(parts, 1)
+                        hit = (new == eos).int().argmax(1)  # first eos per row (every row has one: all are finished)
+                        done = int(hit.max()) + 1
+                        break
+            new = torch.cat(parts, 1)[:, :done]
+        else:
+            position_ids = None
+            if attention_mask is not None:
+                position_ids = (attention_mask.long().cumsum(-1) - 1).masked_fill(attention_mask == 0, 1)
+            out = self(input_ids=prompt, images=images, attention_mask=attention_mask, position_ids=position_ids, use_cache=True,
+                       return_dict=True)
+            past, mask = out.past_key_values, attention_mask
+            out_buf = torch.zeros(n_new, B, dtype=torch.long, device=dev)
+            ftok = forced.t().contiguous() if forced is not None else None
+            fmk = fm.t().contiguous() if fm is not None else None
+            finished = torch.zeros(B, dtype=torch.bool, device=dev)
+            seed_t = torch.tensor([seed], dtype=torch.long, device=dev)
+            step_t = torch.zeros(1, dtype=torch.long, device=dev)
+            tok = torch.empty(B, dtype=torch.long, device=dev)
+            uni = torch.zeros(B, dtype=torch.float32, device=dev) if greedy else None
+            for i in range(n_new):
+                scores = out.logits[:, -1].float()
+                from . import ops
+                ops.sample_logits(scores, temperature, top_k, top_p, vocab_limit=V, seed=seed_t, step=step_t, out_tokens=out_buf,
+                                  force_tok=ftok, force_mask=fmk, eos=eos, pad=pad, finished=finished if eos >= 0 else None,
+                                  tok_out=tok, advance_step=True, uniforms=uni)
+                if crit and stop_after(out_buf[: i + 1].t(), scores):
+                    done = i + 1
+                    break
+                if eos >= 0 and bool(finished.all()):
+                    done = i + 1
+                    break
+                if i + 1 == n_new:
+                    break
+                pos = None
+                if mask is not None:
+                    mask = torch.cat([mask, mask.new_ones(B, 1)], dim=1)
+                    pos = (mask.long().sum(-1) - 1)[:, None]
+                out = self(input_ids=tok[:, None].clone(), past_key_values=past, attention_mask=mask, position_ids=pos, use_cache=True,
+                           return_dict=True)
+                past = out.past_key_values
+            new = out_buf[:done].t()
+        if tokens is not None:
+            tokens[:, s0:s0 + new.shape[1]] = new
+            return tokens, done
+        return torch.cat([input_ids, new], dim=1), done
+
+    @torch.no_grad()
+    def generate(self, input_ids=None, attention_mask=None, images=None, max_new_tokens=None, max_length=None, do_sample=False,
+                 temperature=1.0, top_k=50, top_p=1.0, eos_token_id=None, pad_token_id=None, stopping_criteria=None, generator=None,
+                 fast=None, use_graph=True, **kwargs):
+        """The `model.generate(...)` of the reference's callers (transformers 4.35.2 `GenerationMixin`, which the installed
+        transformers no longer gives this class): omni/eval/vqa/vqa_inference.py:111-137 (`do_sample=True, temperature=0.2,
+        stopping_criteria`), omni/train/trainer.py:1182 (`max_length=128`).  Defaults are 4.35.2's GenerationConfig: greedy
+        (`do_sample=False`), temperature 1.0, top-k 50, top-p 1.0, `max_length` 20 unless `max_new_tokens` is given, eos from
+        the config, pad = eos when the config has none.  Sampling applies temperature, then top-k, then top-p over the whole
+        vocabulary (`dllm_sample_logits`); u is Philox4x32-10 keyed by one int64 drawn from `generator` or torch's default CPU
+        generator per call -- reproducible under `torch.manual_seed`, but NOT torch.multinomial's stream.
+
+        `attention_mask`: LEFT padding (HF batched callers).  Returns LongTensor [B, S + n]: rows that emitted eos are padded with
+        pad; the output ends at the first step where every row is finished or a stopping criterion (callable (ids, scores) ->
+        bool | BoolTensor, a tensor counting when `.all()`; scores = that step's fp32 logits) returns True.  `images` go to the
+        prefill only.  `fast` (default: batch <= 8) runs the decode kernels with one graph replay per token (one per host check
+        when stopping criteria are given, chunks of 16 with eos only); otherwise the model forward is re-entered per token.
+        Beam search, multiple return sequences, repetition penalty and the other unimplemented generation arguments raise
+        NotImplementedError naming the argument; unknown keywords raise TypeError."""
+        for name, value in kwargs.items():
+            if name in self._GENERATE_UNSUPPORTED:
+                if value != self._GENERATE_UNSUPPORTED[name]:
+                    raise NotImplementedError(f"generate: `{name}={value!r}` is not supported (only greedy search and sampling are)")
+            elif name not in self._GENERATE_IGNORED:
+                raise TypeError(f"generate() got an unexpected keyword argument '{name}'")
+        if input_ids is None:
+            raise ValueError("generate: input_ids is required")
+        if stopping_criteria is not None and not all(callable(c) for c in stopping_criteria):
+            raise TypeError("generate: stopping_criteria entries must be callables (ids, scores) -> bool | BoolTensor")
+        if do_sample and not temperature > 0:
+            raise ValueError(f"generate: `temperature` has to be a strictly positive float when sampling, got {temperature}")
+        if not 0.0 <= float(top_p) <= 1.0:
+            raise ValueError(f"generate: `top_p` must be in [0, 1], got {top_p}")
+        if top_k is not None and int(top_k) < 0:
+            raise ValueError(f"generate: `top_k` must be >= 0, got {top_k}")
+        if input_ids.dim() != 2:
+            raise ValueError("generate: input_ids must be [batch, seq]")
+        B, S = input_ids.shape
+        if max_new_tokens is None:
+            max_new_tokens = (20 if max_length is None else int(max_length)) - S
+        max_new_tokens = int(max_new_tokens)
+        if eos_token_id is None:
+            eos_token_id = self.config.eos_token_id
+        if isinstance(eos_token_id, (list, tuple)):
+            if len(eos_token_id) != 1:
+                raise NotImplementedError("generate: several eos_token_id values are not supported")
+            eos_token_id = eos_token_id[0]
+        if pad_token_id is None:
+            pad_token_id = self.config.pad_token_id if self.config.pad_token_id is not None else eos_token_id
+        if pad_token_id is None:
+            pad_token_id = 0
+        if max_new_tokens <= 0:
+            return input_ids
+        seed = self._draw_seed(generator)
+        greedy = not do_sample
+        if greedy:
+            # greedy search over the whole vocabulary: top-k 1 keeps the arg-max ties, u = 0 draws the first of them (argmax's choice)
+            temperature, top_k, top_p = 1.0, 1, 1.0
+        return self._sampled_decode(input_ids, max_new_tokens, float(temperature), int(top_k or 0), float(top_p), None, images,
+                                    attention_mask, None, seed, fast, use_graph, eos=eos_token_id, pad=int(pad_token_id),
+                                    stopping_criteria=stopping_criteria, greedy=greedy)[0]
+
     @torch.no_grad()
     def get_prompt_embeds(self, input_ids, attention_mask=None, images=None):
         """Prompt -> dream-query hidden states (modeling_dreamllm.py:1598-1672): prefill the text with a KV cache, then run

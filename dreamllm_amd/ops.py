@@ -1681,6 +1681,69 @@ def gemv_attn_combine(ws, w, B, H, D, nsplit, residual=None, out_dtype=torch.bfl
     return y
 
 
+def _device_i64(x, device):
+    if isinstance(x, torch.Tensor):
+        if x.dtype != torch.int64 or x.numel() < 1 or x.device != device:
+            raise TypeError("sample_logits: seed / step tensors must be int64 on the logits' device")
+        return x
+    return torch.tensor([int(x)], dtype=torch.int64, device=device)
+
+
+def sample_logits(logits, temperature, top_k=0, top_p=1.0, vocab_limit=None, seed=0, step=0, uniforms=None, *, u_out=None,
+                  kept_out=None, status=None, tok_out=None, out_tokens=None, force_tok=None, force_mask=None, eos=-1, pad=0,
+                  finished=None, advance_step=False, arrive=None):
+    """One sampled token per row of `logits` [B, >= V] (`dllm_sample_logits`; semantics in csrc/sample.hip): temperature, then top-k
+    (0 or >= V: off), then top-p (>= 1: off) over ids < `vocab_limit` (None: every column, at most 32768), the draw with u from
+    `uniforms` [B] fp32 or from Philox4x32-10 keyed by `seed` at counter (row, `step`).  `seed` / `step`: ints or int64 device tensors
+    (read by the kernel, so a captured graph sees their current values).  Returns `tok_out` (int64 [B]).
+
+    Decode-session bookkeeping (all optional, device tensors): `out_tokens` / `force_tok` int64 and `force_mask` bool of shape
+    [n, B] indexed by the step; `eos` >= 0 with `finished` bool [B] (finished rows emit `pad`); `advance_step` adds one to the
+    `step` tensor in the same launch (`arrive`: int32 [1], zero at rest).  `u_out` fp32 [B] / `kept_out` int32 [B] / `status` int32
+    [B] (1 = the row had a NaN or no finite maximum: id 0 emitted) report per row."""
+    _need_gpu(logits)
+    if logits.dim() != 2:
+        raise ValueError("sample_logits: logits must be [B, V]")
+    if logits.dtype != torch.float32:
+        logits = logits.float()
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    B, C = logits.shape
+    V = C if vocab_limit is None else min(int(vocab_limit), C)
+    if not 0 < V <= 32768:
+        raise ValueError(f"sample_logits: vocabulary limit {V} outside 1..32768")
+    if not temperature > 0:
+        raise ValueError("sample_logits: temperature must be > 0 (temperature 0 is greedy: argmax)")
+    dev = logits.device
+    step_t = _device_i64(step, dev)
+    seed_t = None if uniforms is not None else _device_i64(seed, dev)
+    if uniforms is not None and (uniforms.dtype != torch.float32 or uniforms.numel() != B or not uniforms.is_contiguous()):
+        raise TypeError("sample_logits: uniforms must be a contiguous fp32 [B] tensor")
+    if status is None:
+        status = torch.zeros(B, dtype=torch.int32, device=dev)
+    if tok_out is None:
+        tok_out = torch.empty(B, dtype=torch.int64, device=dev)
+    if advance_step and arrive is None:
+        arrive = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_steps = 0
+    for t in (out_tokens, force_tok, force_mask):
+        if t is not None:
+            if t.dim() != 2 or t.shape[1] != B or not t.is_contiguous():
+                raise ValueError("sample_logits: out_tokens / force_tok / force_mask must be contiguous [n, B]")
+            n_steps = t.shape[0] if n_steps == 0 else min(n_steps, t.shape[0])
+    if force_mask is not None and (force_tok is None or force_mask.dtype != torch.bool):
+        raise TypeError("sample_logits: force_mask (bool) needs force_tok")
+    if eos is not None and eos >= 0 and (finished is None or finished.dtype != torch.bool):
+        raise TypeError("sample_logits: eos needs a bool `finished` [B] tensor")
+    k = int(top_k) if top_k is not None else 0
+    k = 0 if k >= V else max(k, 0)
+    check("dllm_sample_logits", _p(logits), logits.stride(0), B, V, float(temperature), k, float(top_p), _p(seed_t), _p(step_t),
+          _p(arrive), int(bool(advance_step)), _p(uniforms), _p(force_tok), _p(force_mask), n_steps,
+          -1 if eos is None else int(eos), int(pad), _p(finished), _p(out_tokens), _p(tok_out), _p(u_out), _p(kept_out), _p(status),
+          _stream())
+    return tok_out
+
+
 # --------------------------------------------------------------------------------------------- torch.compile coexistence
 _DYNAMO_OPAQUE = False
 

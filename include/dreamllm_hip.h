@@ -278,6 +278,23 @@ int dllm_gemv_fused(const void* x, const void* norm_w, float eps, const void* W0
 int dllm_rope_append(void* q, const void* k, const void* v, void* kcache, void* vcache, const float* cos_tab, const float* sin_tab,
                      const int64_t* pos, const int* kv_len, int B, int H, int Hkv, int D, int64_t q_sb, int64_t kv_sb, int64_t c_sb,
                      int64_t c_ss, int64_t c_sh, void* stream);
+/* Sampled token choice of a decode step (csrc/sample.hip; omni/eval/language_eval/modeling_dreamllm.py:36-43,86-91 `sample_top_p`,
+ * omni/eval/vqa/vqa_inference.py:111-137 `generate(do_sample=True)` = transformers 4.35.2 [ext] temperature -> top-k -> top-p ->
+ * multinomial).  One block per row of fp32 logits [B][ld], V <= 32768 ids considered (ids >= V are never emitted):
+ * s = logits * (1 / temperature) (temperature > 0); top-k (0 < top_k < V) keeps s_i >= the k-th largest s, ties kept; top-p (top_p < 1)
+ * keeps i iff the softmax mass of the kept ids with a strictly larger value is <= top_p (the maximum is always kept); the token is the
+ * smallest kept id with (kept mass up to it) > u * (kept mass).  u = uniforms[b] if given, else Philox4x32-10 with key *seed and
+ * counter (b, step lo, step hi, 0), u = (x0 >> 8) * 2^-24; *seed and *step are read from device memory (graph-replay safe).
+ * A row holding a NaN or without a finite maximum emits 0 and sets status[b] = 1 (never cleared).  Bookkeeping of the same launch,
+ * with st = *step: if st < n_steps and force_mask[st * B + b] (bool, may be NULL), the token is force_tok[st * B + b]; with eos >= 0,
+ * finished[b] (bool) rows emit pad and a row that emits eos unforced sets finished[b]; out_tokens[st * B + b] (st < n_steps) and
+ * tok_out[b] receive the token; step_inc != 0: the last block advances *step by one (arrive: int32 zero at rest).  u_out[b] (the u
+ * used) and kept_out[b] (number of kept ids) are optional diagnostics; every output pointer but status may be NULL.  Deterministic:
+ * no float atomics, the same inputs give the same bits. */
+int dllm_sample_logits(const float* logits, int64_t ld, int B, int V, float temperature, int top_k, float top_p, const int64_t* seed,
+                       int64_t* step, int* arrive, int step_inc, const float* uniforms, const int64_t* force_tok, const void* force_mask,
+                       int64_t n_steps, int64_t eos, int64_t pad, void* finished, int64_t* out_tokens, int64_t* tok_out, float* u_out,
+                       int* kept_out, int* status, void* stream);
 int64_t dllm_attn_decode_ws_floats(int B, int H, int D, int nsplit);
 int dllm_attn_decode(const void* q, const void* kcache, const void* vcache, const int* kv_len, const int* kv_start, void* out,
                      float* ws, int B, int H, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t c_sb, int64_t c_ss, int64_t c_sh, int64_t o_sb,
