@@ -498,11 +498,15 @@ struct RopeNew {
     int64_t o_sb, o_sh;
 };
 
-template <int D, bool ROPE>
+// MAP (beam search, csrc/beam.hip): the copy-free KV cache -- key slot j of sequence b is read from cache row row_map[b * map_ld + j]
+// (int32; an entry outside [0, B) reads row b) instead of row b.  The step's own token is still written to, and read from, row b.
+// A separate instantiation: the MAP == false kernels are the ones greedy / sampled decoding always ran.
+template <int D, bool ROPE, bool MAP>
 __global__ __launch_bounds__(256) void attn_decode_partial_kernel(const bf16* __restrict__ q, bf16* __restrict__ kc,
                                                                   bf16* __restrict__ vc, const int* __restrict__ kv_len,
                                                                   const int* __restrict__ kv_start, float* __restrict__ ws, int H, int Hkv, int64_t q_sb, int64_t q_sh,
-                                                                  int64_t c_sb, int64_t c_ss, int64_t c_sh, float scale, int NS, RopeNew rn) {
+                                                                  int64_t c_sb, int64_t c_ss, int64_t c_sh, float scale, int NS, RopeNew rn,
+                                                                  const int* __restrict__ row_map, int64_t map_ld, int nrows) {
     constexpr int LPK = D / 8;    // lanes per key
     constexpr int KPW = 64 / LPK;  // keys per wave per iteration
     __shared__ float lds[4][D + 2];
@@ -561,8 +565,13 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(const bf16* __
         for (int p_ = 0; p_ < PF; ++p_) {
             const int key = key0 + p_ * 4 * KPW;
             const int kk = key < k_end ? key : k_end - 1;
-            kq[p_] = ld_bf16x8(kbase + (int64_t)kk * c_ss);
-            vq[p_] = ld_bf16x8(vbase + (int64_t)kk * c_ss);
+            int64_t roff = 0;
+            if constexpr (MAP) {
+                const int src = row_map[(int64_t)b * map_ld + start + kk];
+                roff = ((unsigned)src < (unsigned)nrows ? (int64_t)(src - b) : 0) * c_sb;
+            }
+            kq[p_] = ld_bf16x8(kbase + roff + (int64_t)kk * c_ss);
+            vq[p_] = ld_bf16x8(vbase + roff + (int64_t)kk * c_ss);
         }
 #pragma unroll
         for (int p_ = 0; p_ < PF; ++p_) {
@@ -688,11 +697,16 @@ __global__ __launch_bounds__(D) void attn_decode_combine_kernel(const float* __r
 
 static int launch_attn_decode(const void* q, void* kcache, void* vcache, const int* kv_len, const int* kv_start, void* out, float* ws,
                               int B, int H, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t c_sb, int64_t c_ss, int64_t c_sh,
-                              int64_t o_sb, int64_t o_sh, float scale, int nsplit, RopeNew rn, bool rope, hipStream_t s) {
+                              int64_t o_sb, int64_t o_sh, float scale, int nsplit, RopeNew rn, bool rope, const int* row_map,
+                              int64_t map_ld, hipStream_t s) {
     const dim3 grid((unsigned)(B * H), (unsigned)nsplit);
+#define DLLM_ATTN_DEC_M(DD, RR, MM)                                                                                                \
+    hipLaunchKernelGGL((attn_decode_partial_kernel<DD, RR, MM>), grid, dim3(256), 0, s, (const bf16*)q, (bf16*)kcache,            \
+                       (bf16*)vcache, kv_len, kv_start, ws, H, Hkv, q_sb, q_sh, c_sb, c_ss, c_sh, scale, nsplit, rn, row_map, map_ld, B)
 #define DLLM_ATTN_DEC(DD, RR)                                                                                                     \
-    hipLaunchKernelGGL((attn_decode_partial_kernel<DD, RR>), grid, dim3(256), 0, s, (const bf16*)q, (bf16*)kcache, (bf16*)vcache,  \
-                       kv_len, kv_start, ws, H, Hkv, q_sb, q_sh, c_sb, c_ss, c_sh, scale, nsplit, rn)
+    do {                                                                                                                          \
+        if (row_map != nullptr) DLLM_ATTN_DEC_M(DD, RR, true); else DLLM_ATTN_DEC_M(DD, RR, false);                             \
+    } while (0)
     const bool fused_combine = (rope && rn.counters != nullptr) || out == nullptr;   // out == NULL: the consumer merges the partials (dllm_gemv_attn_combine)
     if (D == 128) {
         if (rope) DLLM_ATTN_DEC(128, true); else DLLM_ATTN_DEC(128, false);
@@ -706,6 +720,7 @@ static int launch_attn_decode(const void* q, void* kcache, void* vcache, const i
                                o_sh, nsplit);
     }
 #undef DLLM_ATTN_DEC
+#undef DLLM_ATTN_DEC_M
     return dllm_check_launch();
 }
 
@@ -834,16 +849,18 @@ int dllm_gemv_attn_combine(const float* ws, const void* W, void* y, const void* 
 // One query token per (b, h) against a KV cache [B][S_max][Hkv][D] (element strides c_sb, c_ss, c_sh; d contiguous) whose valid
 // length per batch element is read from DEVICE memory (kv_len[b], positions 0 .. kv_len[b]-1 attended).  q / out: [B][H][D]
 // views with strides (q_sb, q_sh) / (o_sb, o_sh).  Same math as the 1-token case of DreamLLMAttention (softmax(q K^T * scale) V).
-int dllm_attn_decode(const void* q, const void* kcache, const void* vcache, const int* kv_len, const int* kv_start, void* out, float* ws, int B, int H,
-                     int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t c_sb, int64_t c_ss, int64_t c_sh, int64_t o_sb,
-                     int64_t o_sh, float scale, int nsplit, void* stream) {
+// row_map (int32 [B][map_ld] or NULL): key slot j of sequence b is read from cache row row_map[b * map_ld + j] (beam search's
+// copy-free cache; map_ld >= the largest kv_len).
+int dllm_attn_decode(const void* q, const void* kcache, const void* vcache, const int* kv_len, const int* kv_start, const int* row_map,
+                     int64_t map_ld, void* out, float* ws, int B, int H, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t c_sb,
+                     int64_t c_ss, int64_t c_sh, int64_t o_sb, int64_t o_sh, float scale, int nsplit, void* stream) {
     if (B < 0 || H <= 0 || Hkv <= 0 || (H % Hkv) != 0 || nsplit < 1 || nsplit > 64) return DLLM_ERR_SHAPE;
     if (D != 64 && D != 128) return DLLM_ERR_SHAPE;
     if ((q_sb | q_sh | c_sb | c_ss | c_sh) & 7) return DLLM_ERR_ALIGN;
-    if (kv_len == nullptr || ws == nullptr) return DLLM_ERR_SHAPE;
+    if (kv_len == nullptr || ws == nullptr || (row_map != nullptr && map_ld < 1)) return DLLM_ERR_SHAPE;
     if (B == 0) return DLLM_OK;
     return launch_attn_decode(q, const_cast<void*>(kcache), const_cast<void*>(vcache), kv_len, kv_start, out, ws, B, H, Hkv, D, q_sb, q_sh,
-                              c_sb, c_ss, c_sh, o_sb, o_sh, scale, nsplit, RopeNew{}, false, (hipStream_t)stream);
+                              c_sb, c_ss, c_sh, o_sb, o_sh, scale, nsplit, RopeNew{}, false, row_map, map_ld, (hipStream_t)stream);
 }
 
 // dllm_attn_decode with the step's RoPE and KV-cache append folded in (replaces dllm_rope_append + dllm_attn_decode: one launch
@@ -851,21 +868,22 @@ int dllm_attn_decode(const void* q, const void* kcache, const void* vcache, cons
 // the new token's key / value, written -- k rotated with rotary position pos[b] -- to cache slot kv_len[b] - 1 and attended to in
 // the same launch.  cos_tab / sin_tab: fp32 [max_pos][D/2]; pos: int64 [B] on device.  counters: int32 [B * H], zero on entry and
 // left zero, or NULL: with counters the split that finishes last merges the partial softmax states inside the launch (no combine
-// launch: 5 launches per layer and token); one counter array per stream in flight.
+// launch: 5 launches per layer and token); one counter array per stream in flight.  row_map / map_ld: as dllm_attn_decode (the
+// new token is written to, and read from, the sequence's own row).
 int dllm_attn_decode_rope(const void* q, const void* k_new, const void* v_new, void* kcache, void* vcache, const float* cos_tab,
-                          const float* sin_tab, const int64_t* pos, const int* kv_len, const int* kv_start, void* out, float* ws,
-                          int* counters, int B, int H, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t kv_sb, int64_t c_sb,
+                          const float* sin_tab, const int64_t* pos, const int* kv_len, const int* kv_start, const int* row_map,
+                          int64_t map_ld, void* out, float* ws, int* counters, int B, int H, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t kv_sb, int64_t c_sb,
                           int64_t c_ss, int64_t c_sh, int64_t o_sb, int64_t o_sh, float scale, int nsplit, void* stream) {
     if (B < 0 || H <= 0 || Hkv <= 0 || (H % Hkv) != 0 || nsplit < 1 || nsplit > 64) return DLLM_ERR_SHAPE;
     if (D != 64 && D != 128) return DLLM_ERR_SHAPE;
     if ((q_sb | q_sh | c_sb | c_ss | c_sh | kv_sb) & 7) return DLLM_ERR_ALIGN;
     if (kv_len == nullptr || ws == nullptr || pos == nullptr || k_new == nullptr || v_new == nullptr || cos_tab == nullptr ||
-        sin_tab == nullptr)
+        sin_tab == nullptr || (row_map != nullptr && map_ld < 1))
         return DLLM_ERR_SHAPE;
     if (B == 0) return DLLM_OK;
     RopeNew rn{(const bf16*)k_new, (const bf16*)v_new, kv_sb, cos_tab, sin_tab, pos, counters, (bf16*)out, o_sb, o_sh};
     return launch_attn_decode(q, kcache, vcache, kv_len, kv_start, out, ws, B, H, Hkv, D, q_sb, q_sh, c_sb, c_ss, c_sh, o_sb, o_sh,
-                              scale, nsplit, rn, true, (hipStream_t)stream);
+                              scale, nsplit, rn, true, row_map, map_ld, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -63,6 +63,7 @@ class GreedyDecodeSession:
         self.force_mask = torch.zeros(max_len, batch_size, dtype=torch.bool, device=dev)
         rope = model.model.layers[0].self_attn.rotary_emb
         self.cos, self.sin = rope.tables(max_len, dev)
+        self.row_map = None  # beam search: int32 [B, max_len] copy-free KV map (BeamDecodeSession); None = every row reads itself
         self.graph = None
         self.logits = None
 
@@ -86,7 +87,8 @@ class GreedyDecodeSession:
                     # round 6: 5 launches per layer -- the split-KV partials go straight into the o projection, whose blocks merge them
                     # while staging x (no combine launch)
                     ws = ops.attn_decode_rope(q, k.view(B, Hkv, D), v.view(B, Hkv, D), self.kc[li], self.vc[li], self.kv_len, self.cos,
-                                              self.sin, pos, 1.0 / math.sqrt(D), self.nsplit, kv_start=self.kv_start, partials_only=True)
+                                              self.sin, pos, 1.0 / math.sqrt(D), self.nsplit, kv_start=self.kv_start, partials_only=True,
+                                              row_map=self.row_map)
                     x2 = ops.gemv_attn_combine(ws, at.o_proj.weight, B, H, D, self.nsplit, residual=x)
                     act = ops.gemv_fused(x2, (mlp.gate_proj.weight, mlp.up_proj.weight), norm_w=layer.post_attention_layernorm.weight,
                                          eps=eps, swiglu=True)
@@ -95,12 +97,12 @@ class GreedyDecodeSession:
                 if self.fuse_rope:   # RoPE + cache append inside the attention launch (round 4)
                     o = ops.attn_decode_rope(q, k.view(B, Hkv, D), v.view(B, Hkv, D), self.kc[li], self.vc[li], self.kv_len, self.cos,
                                              self.sin, pos, 1.0 / math.sqrt(D), self.nsplit, kv_start=self.kv_start,
-                                             counters=self.attn_counters)
+                                             counters=self.attn_counters, row_map=self.row_map)
                 else:
                     ops.rope_append_(q, k.view(B, Hkv, D), v.view(B, Hkv, D), self.kc[li], self.vc[li], self.cos, self.sin, pos,
                                      kv_len=self.kv_len)
                     o = ops.attn_decode(q, self.kc[li], self.vc[li], self.kv_len, 1.0 / math.sqrt(D), self.nsplit,
-                                        kv_start=self.kv_start)
+                                        kv_start=self.kv_start, row_map=self.row_map)
                 x2 = ops.gemv(o.view(B, H * D), at.o_proj.weight, residual=x)
                 act = ops.gemv_fused(x2, (mlp.gate_proj.weight, mlp.up_proj.weight), norm_w=layer.post_attention_layernorm.weight,
                                      eps=eps, swiglu=True)
@@ -115,7 +117,7 @@ class GreedyDecodeSession:
             self.kc[li].view(B * self.max_len, Hkv * D).index_copy_(0, self.slot, k.view(B, Hkv * D))
             self.vc[li].view(B * self.max_len, Hkv * D).index_copy_(0, self.slot, v)
             o = ops.attn_decode(q.view(B, H, D), self.kc[li], self.vc[li], self.kv_len, 1.0 / math.sqrt(D), self.nsplit,
-                                kv_start=self.kv_start)
+                                kv_start=self.kv_start, row_map=self.row_map)
             x2 = ops.gemv(o.view(B, H * D), at.o_proj.weight, residual=x)
             h2, _, _ = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, eps)
             g = ops.gemv(h2, mlp.gate_proj.weight)
@@ -302,3 +304,75 @@ class SampledDecodeSession(GreedyDecodeSession):
         self.seed.fill_(int(seed))
         return super().prefill(input_ids, images=images, attention_mask=attention_mask, forced_tokens=forced_tokens,
                                forced_mask=forced_mask)
+
+
+class BeamDecodeSession(GreedyDecodeSession):
+    """Beam search on the decode kernels: a `GreedyDecodeSession` over B * nb rows (row r = b * nb + beam) whose token choice is
+    `ops.beam_step` (csrc/beam.hip, one launch inside the captured graph) and whose attention reads the cache through a row map.
+
+    The KV cache is never copied or reordered: each row writes its own token to its own slot, and `row_map[r, j]` names the row
+    whose cache holds slot j of beam r's history.  The beam step permutes the map (map[r, :c + 1] = map[parent(r), :c + 1],
+    map[r, c + 1] = r); entries only ever point at older slots, which nobody writes again.  The prompt is prefilled once per batch
+    into row b * nb, and every beam's map points there.  Step 0 (from the prefill's logits) is HF's step 0: the beams with score
+    -1e9 cannot be chosen, so it runs the same kernel on the prompt logits repeated nb times."""
+
+    def __init__(self, model, batch_size: int, num_beams: int, max_len: int, eos: int | None = None, pad: int = 0,
+                 length_penalty: float = 1.0, early_stopping=False, max_new: int = 0, **kw):
+        if batch_size * num_beams > 8:
+            raise ValueError("BeamDecodeSession: the decode GEMV handles up to 8 rows (batch * num_beams) per step")
+        super().__init__(model, batch_size * num_beams, max_len, vocab_limit=None, **kw)
+        dev = self.tok.device
+        self.nbatch, self.nb = batch_size, num_beams
+        self.eos, self.pad = (-1 if eos is None else int(eos)), int(pad)
+        self.length_penalty, self.early_stopping, self.max_new = float(length_penalty), early_stopping, int(max_new)
+        self.beam = ops.BeamState(batch_size, num_beams, max_len + 1, dev)
+        self.tok = self.beam.tok  # the beam step writes the next tokens where the token step reads them
+        self.row_map = torch.zeros(self.B, max_len, dtype=torch.int32, device=dev)
+
+    def _choose(self, logits):
+        ops.beam_step(logits, self.beam, eos=self.eos, pad=self.pad, length_penalty=self.length_penalty,
+                      early_stopping=self.early_stopping, max_new=self.max_new, kv_len=self.kv_len, row_map=self.row_map)
+
+    def _state(self):
+        return super()._state() + self.beam.tensors() + (self.row_map,)
+
+    @torch.no_grad()
+    def prefill(self, input_ids, images=None, attention_mask=None):
+        """Prompt [B, S] (LEFT-padded with `attention_mask`) through the model once per batch; its K/V go to row b * nb, every beam's
+        map points there; then beam step 0 from the last-position logits.  Returns the step's tokens [B * nb]."""
+        B, S = input_ids.shape
+        nb, R = self.nb, self.B
+        if B != self.nbatch or S >= self.max_len:
+            raise ValueError(f"prompt [{B},{S}] does not fit the session (batch {self.nbatch}, max_len {self.max_len})")
+        dev = self.tok.device
+        position_ids, lens = None, None
+        if attention_mask is not None:
+            am = attention_mask.to(dev) != 0
+            lens = am.sum(-1)
+            start = S - lens
+            if not bool(((torch.arange(S, device=dev)[None] >= start[:, None]) == am).all()):
+                raise ValueError("BeamDecodeSession.prefill: attention_mask must be LEFT-padded")
+            position_ids = (am.long().cumsum(-1) - 1).masked_fill(~am, 1)
+            self.kv_start.copy_(start.to(torch.int32).repeat_interleave(nb))
+        else:
+            self.kv_start.zero_()
+        out = self.model(input_ids=input_ids, images=images, attention_mask=attention_mask, position_ids=position_ids,
+                         use_cache=True, return_dict=True)
+        for li, (k, v) in enumerate(out.past_key_values):  # reference layout [B, Hkv, S, D]
+            self.kc[li][::nb, :S].copy_(k.transpose(1, 2))
+            self.vc[li][::nb, :S].copy_(v.transpose(1, 2))
+        rows = torch.arange(R, device=dev, dtype=torch.int32)
+        self.row_map.copy_((rows // nb * nb)[:, None].expand(R, self.max_len))
+        self.row_map[:, S] = rows
+        self.beam.reset()
+        self.beam.status.zero_()
+        self.first_logits = out.logits[:, -1].float().repeat_interleave(nb, 0)
+        ops.beam_step(self.first_logits, self.beam, eos=self.eos, pad=self.pad, length_penalty=self.length_penalty,
+                      early_stopping=self.early_stopping, max_new=self.max_new)
+        self.pos.copy_((torch.full((B,), S, device=dev) if lens is None else lens).repeat_interleave(nb)[:, None])
+        self.kv_len.fill_(S + 1)
+        self.slot.copy_(torch.arange(R, device=dev) * self.max_len + S)
+        self.step_idx.zero_()
+        self.prompt_len = S
+        self.generated = 0
+        return self.tok.clone()

@@ -1491,8 +1491,19 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
         bool | BoolTensor, a tensor counting when `.all()`; scores = that step's fp32 logits) returns True.  `images` go to the
         prefill only.  `fast` (default: batch <= 8) runs the decode kernels with one graph replay per token (one per host check
         when stopping criteria are given, chunks of 16 with eos only); otherwise the model forward is re-entered per token.
-        Beam search, multiple return sequences, repetition penalty and the other unimplemented generation arguments raise
-        NotImplementedError naming the argument; unknown keywords raise TypeError."""
+        `num_beams > 1` with `do_sample=False` is beam search (`_beam_decode`; `length_penalty`, `early_stopping` True / False /
+        "never", `num_return_sequences <= num_beams`; temperature, top-k and top-p do not apply, as in 4.35.2); it returns
+        [B * num_return_sequences, <= max_length].  Beam sampling, group / constrained beam search, repetition penalty and the other
+        unimplemented generation arguments raise NotImplementedError naming the argument; unknown keywords raise TypeError."""
+        num_beams = kwargs.pop("num_beams", 1)
+        beam_args = {k: kwargs.pop(k) for k in ("num_return_sequences", "length_penalty", "early_stopping") if k in kwargs}
+        beam = num_beams is not None and int(num_beams) > 1
+        if beam and do_sample:
+            raise NotImplementedError(f"generate: `num_beams={num_beams!r}` with do_sample=True (beam sampling) is not supported")
+        if not beam:
+            for name, value in beam_args.items():
+                if value != self._GENERATE_UNSUPPORTED[name]:
+                    raise NotImplementedError(f"generate: `{name}={value!r}` is not supported without beam search (num_beams > 1)")
         for name, value in kwargs.items():
             if name in self._GENERATE_UNSUPPORTED:
                 if value != self._GENERATE_UNSUPPORTED[name]:
@@ -1525,6 +1536,21 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
             pad_token_id = self.config.pad_token_id if self.config.pad_token_id is not None else eos_token_id
         if pad_token_id is None:
             pad_token_id = 0
+        if beam:
+            nb = int(num_beams)
+            nrs = int(beam_args.get("num_return_sequences", 1) or 1)
+            early = beam_args.get("early_stopping", False)
+            length_penalty = float(beam_args.get("length_penalty", 1.0))
+            if nb > 8:
+                raise NotImplementedError(f"generate: `num_beams={nb}`: beam search covers at most 8 beams per prompt")
+            if not 1 <= nrs <= nb:
+                raise ValueError(f"generate: `num_return_sequences` ({nrs}) has to be in 1..num_beams ({nb})")
+            if early not in (True, False, "never"):
+                raise ValueError(f"generate: `early_stopping` must be True, False or 'never', got {early!r}")
+            if max_new_tokens <= 0:
+                return input_ids.repeat_interleave(nrs, 0)
+            return self._beam_decode(input_ids, max_new_tokens, nb, nrs, length_penalty, early, images, attention_mask,
+                                     eos_token_id, int(pad_token_id), stopping_criteria, fast, use_graph)
         if max_new_tokens <= 0:
             return input_ids
         seed = self._draw_seed(generator)
@@ -1535,6 +1561,89 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
         return self._sampled_decode(input_ids, max_new_tokens, float(temperature), int(top_k or 0), float(top_p), None, images,
                                     attention_mask, None, seed, fast, use_graph, eos=eos_token_id, pad=int(pad_token_id),
                                     stopping_criteria=stopping_criteria, greedy=greedy)[0]
+
+    @torch.no_grad()
+    def _beam_decode(self, input_ids, max_new_tokens, nb, nrs, length_penalty, early_stopping, images, attention_mask, eos, pad,
+                     stopping_criteria, fast, use_graph):
+        """Beam search (INTEGRATION.md "Beam search"): every step's candidate selection and bookkeeping is one `dllm_beam_step` launch.
+        Fast path (B * nb <= 8 unless `fast=False`): `decode.BeamDecodeSession`, one graph replay per token over a copy-free KV cache;
+        the host reads the done flags between chunks of 16 replays, or after every replay when stopping criteria are given.
+        Otherwise the model forward is re-entered per token with the cache reordered by `index_select`, as the reference does.
+        Criteria are called as crit(ids [B * nb, S + n] running beams, None)."""
+        from . import ops
+        B, S = input_ids.shape
+        dev = input_ids.device
+        R = B * nb
+        eos = -1 if eos is None else int(eos)
+        max_length = S + max_new_tokens
+        fast = (fast is None or bool(fast)) and R <= 8
+        crit = list(stopping_criteria or [])
+
+        def stop(ids):
+            for c in crit:
+                r = c(ids, None)
+                if bool(r.all()) if isinstance(r, torch.Tensor) else bool(r):
+                    return True
+            return False
+
+        running = input_ids.repeat_interleave(nb, 0)
+
+        def advance(state, i, running):
+            return torch.cat([running.index_select(0, state.parents[i].long()), state.tokens[i][:, None]], 1)
+
+        if fast:
+            from .decode import BeamDecodeSession
+            key = ("beam", B, nb, max_length + 1, use_graph, eos, pad, length_penalty, early_stopping, max_new_tokens)
+            sess = getattr(self, "_decode_session", None)
+            if sess is None or sess[0] != key:
+                sess = (key, BeamDecodeSession(self, B, nb, key[3], eos=eos, pad=pad, length_penalty=length_penalty,
+                                               early_stopping=early_stopping, max_new=max_new_tokens, use_graph=use_graph))
+                self._decode_session = sess
+            sess = sess[1]
+            sess.prefill(input_ids, images=images, attention_mask=attention_mask)
+            state, n = sess.beam, 1
+            if crit:
+                running = advance(state, 0, running)
+            halt = (bool(crit) and stop(running)) or bool(state.done.all())
+            while not halt and n < max_new_tokens:
+                m = 1 if crit else min(16, max_new_tokens - n)  # criteria see every step; the done flags are read between chunks
+                sess.generate(m)
+                if crit:
+                    running = advance(state, n, running)
+                n += m
+                halt = (bool(crit) and stop(running)) or bool(state.done.all())
+        else:
+            position_ids = None
+            if attention_mask is not None:
+                position_ids = (attention_mask.long().cumsum(-1) - 1).masked_fill(attention_mask == 0, 1)
+            out = self(input_ids=input_ids, images=images, attention_mask=attention_mask, position_ids=position_ids, use_cache=True,
+                       return_dict=True)
+            past = tuple((k.repeat_interleave(nb, 0), v.repeat_interleave(nb, 0)) for k, v in out.past_key_values)
+            mask = attention_mask.repeat_interleave(nb, 0) if attention_mask is not None else None
+            scores = out.logits[:, -1].float().repeat_interleave(nb, 0)
+            state = ops.BeamState(B, nb, max_new_tokens + 1, dev)
+            n = 0
+            for i in range(max_new_tokens):
+                ops.beam_step(scores, state, eos=eos, pad=pad, length_penalty=length_penalty, early_stopping=early_stopping,
+                              max_new=max_new_tokens)
+                n = i + 1
+                if crit:
+                    running = advance(state, i, running)
+                    if stop(running):
+                        break
+                if n == max_new_tokens or bool(state.done.all()):
+                    break
+                par = state.parents[i].long()
+                past = tuple((k.index_select(0, par), v.index_select(0, par)) for k, v in past)
+                pos = None
+                if mask is not None:
+                    mask = torch.cat([mask, mask.new_ones(R, 1)], dim=1)
+                    pos = (mask.long().sum(-1) - 1)[:, None]
+                out = self(input_ids=state.tok[:, None].clone(), past_key_values=past, attention_mask=mask, position_ids=pos,
+                           use_cache=True, return_dict=True)
+                past = out.past_key_values
+                scores = out.logits[:, -1].float()
+        return ops.beam_finalize(state, n, input_ids, nrs, max_length, eos, pad, length_penalty)
 
     @torch.no_grad()
     def get_prompt_embeds(self, input_ids, attention_mask=None, images=None):

@@ -1618,10 +1618,21 @@ def gemv(x, w, residual=None, out_dtype=torch.bfloat16, out=None):
     return out
 
 
-def attn_decode(q, kcache, vcache, kv_len, scale=None, nsplit=8, out=None, kv_start=None):
+def _row_map(row_map, B, kcache, name):
+    """(row_map, map_ld) of the copy-free beam cache: int32 [B, >= Smax] on the cache's device with a contiguous last dim, or None."""
+    if row_map is None:
+        return None, 0
+    if row_map.dtype != torch.int32 or row_map.dim() != 2 or row_map.shape[0] != B or row_map.stride(1) != 1 or \
+            row_map.shape[1] < kcache.shape[1] or row_map.device != kcache.device:
+        raise ValueError(f"{name}: row_map must be int32 [B, >= S_max] with a contiguous last dim, on the cache's device")
+    return row_map, row_map.stride(0)
+
+
+def attn_decode(q, kcache, vcache, kv_len, scale=None, nsplit=8, out=None, kv_start=None, row_map=None):
     """q [B,H,D]; kcache/vcache [B,Smax,Hkv,D] (same strides); kv_len int32 [B] ON DEVICE (valid cache length, read by the
     kernel: the launch does not depend on it); kv_start int32 [B] on device or None (first valid slot of a left-padded
-    prompt) -> [B,H,D]."""
+    prompt) -> [B,H,D].  `row_map` (int32 [B, >= Smax] on device, or None): key slot j of sequence b is read from cache row
+    row_map[b, j] -- beam search's copy-free cache (`decode.BeamDecodeSession`)."""
     _need_gpu(q, kcache, vcache, kv_len)
     _bf16(q, kcache, vcache)
     B, H, D = q.shape
@@ -1632,20 +1643,23 @@ def attn_decode(q, kcache, vcache, kv_len, scale=None, nsplit=8, out=None, kv_st
         raise TypeError("attn_decode: kv_len must be int32")
     if out is None:
         out = torch.empty(B, H, D, dtype=q.dtype, device=q.device)
+    rm, map_ld = _row_map(row_map, B, kcache, "attn_decode")
     ws = torch.empty(_lib.lib().dllm_attn_decode_ws_floats(B, H, D, nsplit), dtype=torch.float32, device=q.device)
-    check("dllm_attn_decode", _p(q), _p(kcache), _p(vcache), _p(kv_len), _p(kv_start), _p(out), _p(ws), B, H, Hkv, D, q.stride(0), q.stride(1),
+    check("dllm_attn_decode", _p(q), _p(kcache), _p(vcache), _p(kv_len), _p(kv_start), _p(rm), map_ld, _p(out), _p(ws), B, H, Hkv, D,
+          q.stride(0), q.stride(1),
           kcache.stride(0), kcache.stride(1), kcache.stride(2), out.stride(0), out.stride(1),
           float(scale if scale is not None else D ** -0.5), nsplit, _stream())
     return out
 
 
 def attn_decode_rope(q, k_new, v_new, kcache, vcache, kv_len, cos, sin, pos, scale=None, nsplit=8, out=None, kv_start=None,
-                     counters=None, partials_only=False):
+                     counters=None, partials_only=False, row_map=None):
     """`rope_append_` + `attn_decode` in one launch pair: q [B,H,D] UN-rotated (left untouched), k_new / v_new [B,Hkv,D] the step's
     key / value (k un-rotated); the kernel rotates q in registers, writes rotate(k_new) and v_new to cache slot kv_len[b] - 1 and
     attends to them in the same launch.  pos int64 [B] and kv_len int32 [B] on device.  `counters` (int32 [B*H], zero at rest): the
     last split to finish merges the partial states inside the launch instead of a combine launch.  `partials_only`: no merge at all --
-    returns the split-KV partial states (fp32 [B*H, nsplit, D+2]) for `gemv_attn_combine`, which merges them while it stages its x."""
+    returns the split-KV partial states (fp32 [B*H, nsplit, D+2]) for `gemv_attn_combine`, which merges them while it stages its x.
+    `row_map`: as in `attn_decode` (the step's own k / v are written to, and read from, row b)."""
     _need_gpu(q, k_new, v_new, kcache, vcache, kv_len, cos, sin, pos)
     _bf16(q, k_new, v_new, kcache, vcache)
     B, H, D = q.shape
@@ -1658,9 +1672,10 @@ def attn_decode_rope(q, k_new, v_new, kcache, vcache, kv_len, cos, sin, pos, sca
         raise TypeError("attn_decode_rope: kv_len must be int32, pos int64")
     if out is None and not partials_only:
         out = torch.empty(B, H, D, dtype=q.dtype, device=q.device)
+    rm, map_ld = _row_map(row_map, B, kcache, "attn_decode_rope")
     ws = torch.empty(_lib.lib().dllm_attn_decode_ws_floats(B, H, D, nsplit), dtype=torch.float32, device=q.device)
     check("dllm_attn_decode_rope", _p(q), _p(k_new), _p(v_new), _p(kcache), _p(vcache), _p(cos), _p(sin), _p(pos.reshape(-1)), _p(kv_len),
-          _p(kv_start), _p(None if partials_only else out), _p(ws), _p(None if partials_only else counters), B, H, Hkv, D, q.stride(0), q.stride(1),
+          _p(kv_start), _p(rm), map_ld, _p(None if partials_only else out), _p(ws), _p(None if partials_only else counters), B, H, Hkv, D, q.stride(0), q.stride(1),
           k_new.stride(0), kcache.stride(0), kcache.stride(1), kcache.stride(2), H * D if partials_only else out.stride(0),
           D if partials_only else out.stride(1), float(scale if scale is not None else D ** -0.5), nsplit, _stream())
     return ws if partials_only else out
@@ -1742,6 +1757,129 @@ def sample_logits(logits, temperature, top_k=0, top_p=1.0, vocab_limit=None, see
           -1 if eos is None else int(eos), int(pad), _p(finished), _p(out_tokens), _p(tok_out), _p(u_out), _p(kept_out), _p(status),
           _stream())
     return tok_out
+
+
+# The generated length beam search divides by (an eos hypothesis, is_done): tokens generated before the candidate + BEAM_LEN_OFFSET.
+# 1 = the candidate counted (transformers' `cur_len = input_ids.shape[-1] + 1` of the decoder-only fix; INTEGRATION.md "Beam search").
+BEAM_LEN_OFFSET = 1
+BEAM_EARLY_STOPPING = {False: 0, True: 1, "never": 2}
+
+
+class BeamState:
+    """Device state of a beam search over B batches of nb beams (`dllm_beam_step`): running beams, hypothesis store, done flags, the
+    step counter and the per-step parents / tokens (n_steps rows).  `reset()` starts a search: beam scores [0, -1e9, ...] per batch."""
+
+    def __init__(self, B, nb, n_steps, device):
+        R = B * nb
+        self.B, self.nb, self.n_steps = B, nb, n_steps
+        self.beam_score = torch.zeros(R, dtype=torch.float32, device=device)
+        self.tok = torch.zeros(R, dtype=torch.int64, device=device)
+        self.parents = torch.zeros(n_steps, R, dtype=torch.int32, device=device)
+        self.tokens = torch.zeros(n_steps, R, dtype=torch.int64, device=device)
+        self.step = torch.zeros(1, dtype=torch.int64, device=device)
+        self.arrive = torch.zeros(B + 1, dtype=torch.int32, device=device)
+        self.ws = torch.empty(2 * R * 2 * nb, dtype=torch.float32, device=device)
+        self.hyp_score = torch.zeros(B, nb, dtype=torch.float64, device=device)
+        self.hyp_meta = torch.zeros(B, nb, 3, dtype=torch.int32, device=device)
+        self.hyp_count = torch.zeros(B, dtype=torch.int32, device=device)
+        self.worst = torch.full((B,), 1e9, dtype=torch.float64, device=device)
+        self.done = torch.zeros(B, dtype=torch.int32, device=device)
+        self.status = torch.zeros(R, dtype=torch.int32, device=device)
+        self.reset()
+
+    def reset(self):
+        self.beam_score.view(self.B, self.nb).fill_(-1e9)[:, 0] = 0.0
+        for t in (self.step, self.hyp_count, self.done, self.status, self.arrive):
+            t.zero_()
+        self.worst.fill_(1e9)
+
+    def tensors(self):
+        """Every tensor a step changes (graph capture saves / restores them around the warm-up step)."""
+        return (self.beam_score, self.tok, self.parents, self.tokens, self.step, self.hyp_score, self.hyp_meta, self.hyp_count,
+                self.worst, self.done, self.status)
+
+
+def beam_step(logits, state, eos=-1, pad=0, length_penalty=1.0, early_stopping=False, max_new=0, vocab_limit=None, kv_len=None,
+              row_map=None, cand_score=None, cand_flat=None, len_offset=None):
+    """One beam-search step (`dllm_beam_step`, csrc/beam.hip) over fp32 `logits` [B * nb, >= V] with the device `state` (`BeamState`):
+    candidate selection, hypothesis bookkeeping and the next beams (`state.tok`, `state.beam_score`, `state.parents[step]`,
+    `state.tokens[step]`); advances `state.step`.  No host read: graph-capturable.  `early_stopping`: True / False / "never";
+    `max_new` = max_length - prompt length (used by "never" with length_penalty > 0).  `row_map` + `kv_len` (int32, device): the
+    copy-free KV map is permuted to follow the parents.  `cand_score` fp32 / `cand_flat` int32 [B, 2 nb]: the merged candidates."""
+    import struct
+    _need_gpu(logits)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError("beam_step: logits must be fp32 [rows, V] with a contiguous last dim")
+    B, nb = state.B, state.nb
+    if logits.shape[0] != B * nb:
+        raise ValueError(f"beam_step: logits have {logits.shape[0]} rows, the state {B} x {nb}")
+    V = logits.shape[1] if vocab_limit is None else min(int(vocab_limit), logits.shape[1])
+    if early_stopping not in BEAM_EARLY_STOPPING:
+        raise ValueError(f"beam_step: early_stopping must be True, False or 'never', got {early_stopping!r}")
+    map_ld = 0
+    if row_map is not None:
+        if kv_len is None or row_map.dtype != torch.int32 or row_map.dim() != 2 or row_map.shape[0] != B * nb or row_map.stride(1) != 1:
+            raise ValueError("beam_step: row_map must be int32 [B * nb, map_ld] (contiguous last dim) with kv_len")
+        map_ld = row_map.stride(0)
+    for t in (cand_score, cand_flat):
+        if t is not None and (t.shape != (B, 2 * nb) or not t.is_contiguous()):
+            raise ValueError("beam_step: cand_score / cand_flat must be contiguous [B, 2 * nb]")
+    lp_bits = struct.unpack("<q", struct.pack("<d", float(length_penalty)))[0]
+    check("dllm_beam_step", _p(logits), logits.stride(0), B, nb, V, _p(state.beam_score), _p(state.tok), _p(state.parents),
+          _p(state.tokens), state.n_steps, _p(state.step), _p(state.arrive), _p(state.ws), _p(state.hyp_score), _p(state.hyp_meta),
+          _p(state.hyp_count), _p(state.worst), _p(state.done), -1 if eos is None else int(eos), int(pad), lp_bits,
+          BEAM_EARLY_STOPPING[early_stopping], int(max_new), BEAM_LEN_OFFSET if len_offset is None else int(len_offset),
+          _p(kv_len), _p(row_map), map_ld, _p(cand_score), _p(cand_flat), _p(state.status), _stream())
+    return state.tok
+
+
+def beam_finalize(state, n_steps, prompts, num_return_sequences, max_length, eos, pad, length_penalty):
+    """The end of a beam search, on the host (once per call): batches that are not done add their running beams (generated length
+    = n_steps), then per batch the `num_return_sequences` best hypotheses (sorted ascending by score, popped from the end: the
+    later of two equal scores wins) are rebuilt from the per-step parents / tokens and written from column 0 after their prompt
+    row (`prompts` [B, S]); width min(longest + 1, max_length), pad elsewhere, eos right after every sequence shorter than the
+    width.  Returns LongTensor [B * num_return_sequences, width] on the prompts' device."""
+    B, nb = state.B, state.nb
+    S = prompts.shape[1]
+    par = state.parents[:n_steps].cpu().tolist()
+    tok = state.tokens[:n_steps].cpu().tolist()
+    hs = state.hyp_score.cpu().tolist()
+    hm = state.hyp_meta.cpu().tolist()
+    cnt = state.hyp_count.cpu().tolist()
+    done = state.done.cpu().tolist()
+    bsc = state.beam_score.cpu().tolist()
+    wst = state.worst.cpu().tolist()
+    pr = prompts.cpu().tolist()
+    best = []
+    for b in range(B):
+        hyps = [(hs[b][i], hm[b][i][0], hm[b][i][1], hm[b][i][2]) for i in range(cnt[b])]
+        worst = wst[b]
+        if not done[b]:
+            for j in range(nb):
+                score = float(bsc[b * nb + j]) / (n_steps ** length_penalty)
+                if len(hyps) < nb or score > worst:
+                    hyps.append((score, n_steps, b * nb + j, n_steps))
+                    if len(hyps) > nb:
+                        order = sorted((h[0], i) for i, h in enumerate(hyps))
+                        del hyps[order[0][1]]
+                        worst = order[1][0]
+                    else:
+                        worst = min(score, worst)
+        ranked = sorted(hyps, key=lambda h: h[0])
+        for _ in range(num_return_sequences):
+            _, end_step, row, n = ranked.pop()
+            seq = []
+            for s in range(end_step - 1, end_step - 1 - n, -1):
+                seq.append(tok[s][row])
+                row = par[s][row]
+            best.append(pr[b] + seq[::-1])
+    width = min(max(len(x) for x in best) + 1, max_length)
+    out = torch.full((len(best), width), int(pad), dtype=torch.long)
+    for i, x in enumerate(best):
+        out[i, : len(x)] = torch.tensor(x[:width], dtype=torch.long)
+        if len(x) < width:
+            out[i, len(x)] = int(eos) if eos is not None and int(eos) >= 0 else int(pad)
+    return out.to(prompts.device)
 
 
 # --------------------------------------------------------------------------------------------- torch.compile coexistence

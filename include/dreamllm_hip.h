@@ -295,10 +295,29 @@ int dllm_sample_logits(const float* logits, int64_t ld, int B, int V, float temp
                        int64_t* step, int* arrive, int step_inc, const float* uniforms, const int64_t* force_tok, const void* force_mask,
                        int64_t n_steps, int64_t eos, int64_t pad, void* finished, int64_t* out_tokens, int64_t* tok_out, float* u_out,
                        int* kept_out, int* status, void* stream);
+/* Beam-search step of a decode loop (csrc/beam.hip; omni/eval/vqa/vqa_inference.py:111-119 `generate(num_beams=5)` = transformers
+ * 4.35.2 [ext] beam_search + BeamSearchScorer, rules in INTEGRATION.md "Beam search").  fp32 logits [B * nb][ld], V ids (2 nb <= V,
+ * nb <= 8): per batch the top 2 nb of log_softmax + beam_score (ties: lower beam * V + id first), the hypothesis bookkeeping (hyp_score
+ * double [B][nb], hyp_meta int32 [B][nb][3] = end step, end row, length; hyp_count int32 [B]; worst double [B], 1e9 initially;
+ * done int32 [B]) and the next beams: tok_out / beam_score [B * nb]; with st = *step < n_steps, parents[st][r] (int32, global row)
+ * and tokens[st][r] (int64).  Eos hypotheses and is_done use the generated length *step + len_offset; length_penalty_bits = the
+ * IEEE-754 bits of the double length penalty; early_stopping 0 / 1 / 2 = False / True / "never" (max_new = max_length - prompt
+ * length).  row_map (int32 [B * nb][map_ld], or NULL): map[r][0..c] = map[parent(r)][0..c], map[r][c + 1] = r with c =
+ * kv_len[b * nb] - 1.  ws: B * nb * 2 nb floats + as many ints; arrive: int32 [B + 1], zero at rest; the launch advances *step.
+ * cand_score / cand_flat [B][2 nb] (optional) receive the merged candidates.  A row with a NaN or no finite maximum sets status[r] = 1
+ * and its candidates score -inf.  Deterministic: no float atomics. */
+int dllm_beam_step(const float* logits, int64_t ld, int B, int nb, int V, float* beam_score, int64_t* tok_out, int* parents,
+                   int64_t* tokens, int64_t n_steps, int64_t* step, int* arrive, void* ws, double* hyp_score, int* hyp_meta,
+                   int* hyp_count, double* worst, int* done, int64_t eos, int64_t pad, int64_t length_penalty_bits,
+                   int early_stopping, int max_new, int len_offset, const int* kv_len, int* row_map, int64_t map_ld,
+                   float* cand_score, int* cand_flat, int* status, void* stream);
 int64_t dllm_attn_decode_ws_floats(int B, int H, int D, int nsplit);
-int dllm_attn_decode(const void* q, const void* kcache, const void* vcache, const int* kv_len, const int* kv_start, void* out,
-                     float* ws, int B, int H, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t c_sb, int64_t c_ss, int64_t c_sh, int64_t o_sb,
-                     int64_t o_sh, float scale, int nsplit, void* stream);
+/* row_map (int32 [B][map_ld] on device, or NULL; here and in dllm_attn_decode_rope): beam search's copy-free KV cache -- key slot j
+ * of sequence b is read from cache row row_map[b * map_ld + j] (an entry outside [0, B) reads row b); a separate kernel
+ * instantiation, so calls without a map compute exactly what they did before.  The step's own token stays in row b. */
+int dllm_attn_decode(const void* q, const void* kcache, const void* vcache, const int* kv_len, const int* kv_start, const int* row_map,
+                     int64_t map_ld, void* out, float* ws, int B, int H, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t c_sb,
+                     int64_t c_ss, int64_t c_sh, int64_t o_sb, int64_t o_sh, float scale, int nsplit, void* stream);
 /* dllm_rope_append + dllm_attn_decode in ONE launch pair (round 4; 6 launches per layer and token instead of 7): q [B][H][D]
  * UN-rotated (read only), k_new / v_new [B][Hkv][D] (batch pitch kv_sb, k un-rotated) = the step's key / value.  The attention
  * kernel rotates q in registers (rounded to bf16 as dllm_rope_append stores it), rotates k_new with rotary position pos[b], writes
@@ -308,8 +327,8 @@ int dllm_attn_decode(const void* q, const void* kcache, const void* vcache, cons
  * launch (agent-scope stores / loads around a ticket; fixed split order = the combine kernel's bits), so the combine launch
  * disappears too: 5 launches per layer and token. */
 int dllm_attn_decode_rope(const void* q, const void* k_new, const void* v_new, void* kcache, void* vcache, const float* cos_tab,
-                          const float* sin_tab, const int64_t* pos, const int* kv_len, const int* kv_start, void* out, float* ws,
-                          int* counters, int B, int H, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t kv_sb, int64_t c_sb,
+                          const float* sin_tab, const int64_t* pos, const int* kv_len, const int* kv_start, const int* row_map,
+                          int64_t map_ld, void* out, float* ws, int* counters, int B, int H, int Hkv, int D, int64_t q_sb, int64_t q_sh, int64_t kv_sb, int64_t c_sb,
                           int64_t c_ss, int64_t c_sh, int64_t o_sb, int64_t o_sh, float scale, int nsplit, void* stream);
 /* The o projection of a token step fed directly with the split-KV partials of dllm_attn_decode[_rope] called with out = NULL (round 6):
  * y[M, N] = merge(ws) W^T (+ residual), merge = the combine of the split states (the bits dllm_attn_decode writes to `out`), computed while
