@@ -26,6 +26,39 @@ PluginType = Literal["embedding", "head"]
 PipelineImageType = Any
 
 
+def graph_denoise_mode(use_graph, sched, guidance_scale, guidance_rescale, eta, callback, num_images_per_prompt, in_channels):
+    """Which denoising loop `pipeline` runs (both heads; host logic only):
+      "ddim"  -- deterministic DDIM + CFG, no rescale, no callback: hipGraph replay + `dllm_cfg_ddim_step` (the original fast path);
+      "sched" -- any scheduler with `step_coeffs` (DDPM, DDIM with eta), with or without CFG / rescale / callback: hipGraph replay +
+                 `dllm_cfg_sched_step`;
+      None    -- the plain per-step loop (`use_graph=False`, a scheduler without `step_coeffs`, num_images_per_prompt != 1,
+                 an inpainting-style UNet)."""
+    if not (use_graph and num_images_per_prompt == 1 and in_channels == 4):
+        return None
+    if (guidance_scale > 1.0 and guidance_rescale == 0.0 and eta == 0.0 and hasattr(sched, "step_cfg_fused_")
+            and callback is None):
+        return "ddim"
+    return "sched" if hasattr(sched, "step_coeffs") else None
+
+
+def predraw_step_noise(shape, coeffs, generator, device):
+    """The plain loop's ancestral draws, made ahead of a graphed loop: one `randn_tensor(shape, generator, device, fp32)` (NCHW, as
+    `scheduler.step` draws it) per step whose coefficients draw, in step order -> fp32 [n, B, H, W, C] (NHWC) on `device`, or None
+    when no step draws.  Seeded CPU generators, lists of generators, `generator=None` (the device's default generator: the UNet
+    draws nothing) and `utils.replay_draws` give the plain loop's values bit for bit."""
+    n = sum(1 for c in coeffs if c.draws)
+    if n == 0:
+        return None
+    B, C, H, W = shape
+    out = torch.empty(n, B, H, W, C, dtype=torch.float32, device=device)
+    k = 0
+    for c in coeffs:
+        if c.draws:
+            out[k].copy_(randn_tensor(shape, generator=generator, device=device, dtype=torch.float32).permute(0, 2, 3, 1))
+            k += 1
+    return out
+
+
 class PluginBase(ABC, nn.Module, FSDPMixin):
     """modeling_plugins.py:32-81."""
 
@@ -479,13 +512,19 @@ class StableDiffusionHead(MultimodalHead):
         return guidance_rescale * noise_pred_rescaled + (1 - guidance_rescale) * noise_cfg
 
     @torch.no_grad()
-    def _denoise_loop_graph(self, latents, ctx_embeds, timesteps, sched, guidance_scale, added_cond_kwargs=None):
-        """Deterministic-DDIM + CFG loop body (modeling_plugins.py:809-839) as: [fill t] -> hipGraph replay of one UNet
-        forward on static NHWC buffers -> ONE fused kernel (CFG combine + DDIM update + next UNet input).  ~600 kernel
-        launches per step collapse into one graph launch, which is what the loop is bound by at B_img = 1.  The graph
-        (and its static buffers, including the cross-attention K/V of the conditioning tokens) is cached per shape."""
+    def _denoise_loop_graph(self, latents, ctx_embeds, timesteps, sched, guidance_scale, added_cond_kwargs=None, mode="ddim",
+                            guidance_rescale=0.0, eta=0.0, generator=None, callback=None, callback_steps=1):
+        """The loop body (modeling_plugins.py:809-839) as: [fill t] -> hipGraph replay of one UNet forward on static NHWC
+        buffers -> ONE fused kernel (CFG combine + scheduler update + next UNet input).  ~600 kernel launches per step collapse
+        into one graph launch, which is what the loop is bound by at B_img = 1.  The graph (and its static buffers, including
+        the cross-attention K/V of the conditioning tokens) is cached per shape and CFG factor G.
+        mode "ddim" (see `graph_denoise_mode`): deterministic DDIM + CFG through `dllm_cfg_ddim_step`.  mode "sched": any
+        scheduler with `step_coeffs`, CFG (G = 2) or not (G = 1, the UNet captured at batch B), guidance rescale, ancestral noise
+        drawn ahead of the loop in the plain loop's order (`predraw_step_noise`), `callback(i, t, latents)` as the plain loop."""
         B, C, H, W = latents.shape
-        key = (B, H, W, tuple(ctx_embeds.shape), added_cond_kwargs is not None)
+        do_cfg = guidance_scale > 1.0
+        G = 2 if (mode == "ddim" or do_cfg) else 1
+        key = (B, H, W, tuple(ctx_embeds.shape), added_cond_kwargs is not None, G)
         cache = getattr(self, "_graph_cache", None)
         if cache is None:
             cache = self._graph_cache = {}
@@ -504,15 +543,15 @@ class StableDiffusionHead(MultimodalHead):
             return (id(p), p._version, p.data_ptr(), p.dtype, str(p.device))
         w_sig = tuple(_sig(p) for p in self.unet.time_embedding.parameters()) + \
             tuple(_sig(p) for r in self.unet._resnets() for p in r.time_emb_proj.parameters())
-        tb_key = (ts_host, 2 * B, w_sig)
+        tb_key = (ts_host, G * B, w_sig)
         tb_cache = getattr(self, "_time_bias_cache", None)
         if addk is None and tb_cache is not None and tb_cache[0] == tb_key:
             tb_table = tb_cache[1]
         else:
-            tb_table = self.unet.precompute_time_bias(list(ts_host), 2 * B, addk)
+            tb_table = self.unet.precompute_time_bias(list(ts_host), G * B, addk)
             self._time_bias_cache = (tb_key, tb_table) if addk is None else None
         if ent is None:
-            x_in = torch.zeros(2 * B, H, W, 8, dtype=self.dtype, device=dev)
+            x_in = torch.zeros(G * B, H, W, 8, dtype=self.dtype, device=dev)
             tb_static = tb_table[0].clone()
             ctx_static = {k: [t.clone() for t in v] for k, v in ctx_now.items()}
             emb_static = ctx_embeds.clone()
@@ -536,12 +575,32 @@ class StableDiffusionHead(MultimodalHead):
         lat = latents.permute(0, 2, 3, 1).contiguous().float()  # NHWC fp32 master copy
         x_in = ent["x_in"]
         x_in.zero_()
-        x_in[:B, ..., :4] = lat.to(self.dtype)
-        x_in[B:, ..., :4] = lat.to(self.dtype)
-        for i, t in enumerate(ts_host):  # host floats: no per-step device read of the schedule
+        for g in range(G):
+            x_in[g * B:(g + 1) * B, ..., :4] = lat.to(self.dtype)
+        if mode == "ddim":
+            for i, t in enumerate(ts_host):  # host floats: no per-step device read of the schedule
+                ent["tb"].copy_(tb_table[i])
+                ent["graph"].replay()
+                sched.step_cfg_fused_(ent["pred"], t, lat, x_in, guidance_scale)
+            return lat.permute(0, 3, 1, 2).contiguous()
+        if sched.config.prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(sched.config.prediction_type)
+        vpred = sched.config.prediction_type == "v_prediction"
+        ts_list = list(timesteps.tolist() if torch.is_tensor(timesteps) else timesteps)
+        coeffs = [sched.step_coeffs(t, eta) for t in ts_list]
+        noise = predraw_step_noise(latents.shape, coeffs, generator, dev)
+        phi = guidance_rescale if do_cfg else 0.0  # the reference rescales only with CFG (:829)
+        k = 0
+        for i, (t, c) in enumerate(zip(ts_list, coeffs)):
             ent["tb"].copy_(tb_table[i])
             ent["graph"].replay()
-            sched.step_cfg_fused_(ent["pred"], t, lat, x_in, guidance_scale)
+            z = None
+            if c.draws:
+                z = noise[k]
+                k += 1
+            ops.cfg_sched_step_(ent["pred"], lat, z, x_in, guidance_scale, phi, c, vpred)
+            if callback is not None and i % callback_steps == 0:
+                callback(i, t, lat.permute(0, 3, 1, 2).contiguous())
         return lat.permute(0, 3, 1, 2).contiguous()
 
     @torch.no_grad()
@@ -572,10 +631,12 @@ class StableDiffusionHead(MultimodalHead):
         timesteps = sched.timesteps
         latents = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.config.in_channels, height, width,
                                        torch.float32, device, generator, latents)
-        fused = (use_graph and do_cfg and guidance_rescale == 0.0 and eta == 0.0 and hasattr(sched, "step_cfg_fused_")
-                 and callback is None and num_images_per_prompt == 1 and self.unet.config.in_channels == 4)
-        if fused:
-            latents = self._denoise_loop_graph(latents, prompt_embeds, timesteps.tolist(), sched, guidance_scale)
+        mode = graph_denoise_mode(use_graph, sched, guidance_scale, guidance_rescale, eta, callback, num_images_per_prompt,
+                                  self.unet.config.in_channels)
+        if mode is not None:
+            latents = self._denoise_loop_graph(latents, prompt_embeds, timesteps.tolist(), sched, guidance_scale, mode=mode,
+                                               guidance_rescale=guidance_rescale, eta=eta, generator=generator, callback=callback,
+                                               callback_steps=callback_steps)
         else:
             ctx = self.unet.prepare_context(prompt_embeds)  # cross-attention K/V of the dream tokens: once, not per step
             for i, t in enumerate(timesteps.tolist()):

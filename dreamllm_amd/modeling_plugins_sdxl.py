@@ -26,7 +26,7 @@ from typing import Any, Callable, Literal, Optional, Tuple
 import torch
 
 from . import ops
-from .modeling_plugins import StableDiffusionHead
+from .modeling_plugins import StableDiffusionHead, graph_denoise_mode
 from .projector import build_projector
 from .utils import logger
 
@@ -223,11 +223,12 @@ class StableDiffusionXLHead(StableDiffusionHead):
         latents = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.config.in_channels, height, width,
                                        torch.float32, device, generator, latents)
         added = {"text_embeds": add_text_embeds, "time_ids": add_time_ids}
-        fused = (use_graph and do_cfg and guidance_rescale == 0.0 and eta == 0.0 and hasattr(sched, "step_cfg_fused_")
-                 and callback is None and num_images_per_prompt == 1 and self.unet.config.in_channels == 4)
-        if fused:
+        mode = graph_denoise_mode(use_graph, sched, guidance_scale, guidance_rescale, eta, callback, num_images_per_prompt,
+                                  self.unet.config.in_channels)
+        if mode is not None:
             latents = self._denoise_loop_graph(latents, prompt_embeds, timesteps.tolist(), sched, guidance_scale,
-                                               added_cond_kwargs=added)
+                                               added_cond_kwargs=added, mode=mode, guidance_rescale=guidance_rescale, eta=eta,
+                                               generator=generator, callback=callback, callback_steps=callback_steps)
         else:
             ctx = self.unet.prepare_context(prompt_embeds)
             for i, t in enumerate(timesteps.tolist()):

@@ -1508,6 +1508,28 @@ def cfg_ddim_step_(pred, latents, next_in, guidance, a_t, a_prev, v_prediction=F
     return latents
 
 
+def cfg_sched_step_(pred, latents, noise, next_in, guidance, rescale, coeffs, v_prediction=False):
+    """Fused CFG combine (+ guidance rescale) + scheduler step from `coeffs` (schedulers.StepCoeffs) + next UNet input, in place
+    on the fp32 NHWC latents [B,H,W,4].  pred bf16 [G*B,H,W,4] (G = 2 with CFG, uncond first; G = 1 without), noise fp32 like
+    latents (used when coeffs.sigma != 0) or None, next_in bf16 [G*B,H,W,8] or None."""
+    _need_gpu(pred, latents, noise, next_in)
+    B, P = latents.shape[0], latents.numel() // (4 * max(latents.shape[0], 1))
+    if pred.dtype != torch.bfloat16 or latents.dtype != torch.float32 or latents.shape[-1] != 4 or not latents.is_contiguous():
+        raise ValueError("cfg_sched_step_: pred bf16 [G*B,...,4], latents fp32 contiguous [B,...,4]")
+    G = pred.numel() // max(latents.numel(), 1)
+    if pred.numel() != G * latents.numel() or not pred.is_contiguous():
+        raise ValueError(f"cfg_sched_step_: pred {tuple(pred.shape)} is not G x latents {tuple(latents.shape)}")
+    if noise is not None and (noise.dtype != torch.float32 or noise.shape != latents.shape or not noise.is_contiguous()):
+        raise ValueError("cfg_sched_step_: noise must be fp32 contiguous like latents")
+    if next_in is not None and (next_in.dtype != torch.bfloat16 or next_in.numel() != 2 * G * latents.numel()
+                                or not next_in.is_contiguous()):
+        raise ValueError("cfg_sched_step_: next_in must be bf16 contiguous [G*B,...,8]")
+    c = coeffs
+    check("dllm_cfg_sched_step", _p(pred), _p(latents), _p(noise), _p(next_in), B, P, G, float(guidance), float(rescale),
+          int(v_prediction), c.sqrt_at, c.sqrt_1mat, c.k_x0, c.k_eps, c.k_x, c.sigma, _stream())
+    return latents
+
+
 class PackedAttnFn(torch.autograd.Function):
     """Self-attention on a packed [B,S,3,H,D] QKV GEMM output; the backward writes dQ/dK/dV straight into one packed
     buffer (no zero-filled slice gradients)."""

@@ -2,13 +2,15 @@
 uses them (omni/models/dreamllm/modeling_plugins.py:379-381,534-536,551,787-788,812,833; `_compute_snr` :468-491).
 SD-2.1 scheduler_config: scaled_linear betas 0.00085 -> 0.012 over 1000 steps, steps_offset 1, clip_sample False,
 set_alpha_to_one False, "leading" timestep spacing.  Host-side tables + tiny latent updates; the
-denoising loop's per-step update runs as the fused HIP kernel `dllm_cfg_ddim_step` (see `DDIMScheduler.step_cfg_fused_`).
+denoising loop's per-step update runs as the fused HIP kernel `dllm_cfg_ddim_step` (see `DDIMScheduler.step_cfg_fused_`), or,
+for every other graphed loop, `dllm_cfg_sched_step` on the coefficients of `step_coeffs`.
 """
 from __future__ import annotations
 
 import json
 import os
 from types import SimpleNamespace
+from typing import NamedTuple
 
 import torch
 
@@ -17,6 +19,19 @@ from .utils import randn_tensor
 SD21_SCHED = dict(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                   prediction_type="epsilon", steps_offset=1, clip_sample=False, set_alpha_to_one=False,
                   timestep_spacing="leading", variance_type="fixed_small")
+
+
+class StepCoeffs(NamedTuple):
+    """`step()` at one timestep as plain floats (the operands of the fused HIP step `dllm_cfg_sched_step`):
+    x0 = (x - sqrt_1mat e) / sqrt_at, eps = e  (epsilon)  or  x0 = sqrt_at x - sqrt_1mat e, eps = sqrt_at e + sqrt_1mat x  (v);
+    x_prev = k_x0 x0 + k_eps eps + k_x x + sigma z, with z ~ N(0, 1) drawn (randn_tensor, NCHW) iff `draws`."""
+    sqrt_at: float
+    sqrt_1mat: float
+    k_x0: float
+    k_eps: float
+    k_x: float
+    sigma: float
+    draws: bool
 
 
 def _load_cfg(name_or_path):
@@ -117,6 +132,19 @@ class DDPMScheduler(_SchedulerBase):
             mean = mean + var**0.5 * noise
         return mean.to(sample.dtype)
 
+    def step_coeffs(self, t, eta=0.0):
+        """`step()` at timestep t as StepCoeffs, from the same `.item()` floats (`eta` is ignored, as in `step()`)."""
+        t = int(t)
+        T = self.config.num_train_timesteps
+        prev_t = t - T // (self.num_inference_steps or T)
+        a_t = self.alphas_cumprod[t].item()
+        a_prev = self.alphas_cumprod[prev_t].item() if prev_t >= 0 else 1.0
+        cur_alpha = a_t / a_prev
+        cur_beta = 1 - cur_alpha
+        sigma = max((1 - a_prev) / (1 - a_t) * cur_beta, 1e-20) ** 0.5 if t > 0 else 0.0
+        return StepCoeffs(a_t**0.5, (1 - a_t) ** 0.5, (a_prev**0.5 * cur_beta) / (1 - a_t), 0.0,
+                          cur_alpha**0.5 * (1 - a_prev) / (1 - a_t), sigma, t > 0)
+
 
 class DDIMScheduler(_SchedulerBase):
     """Deterministic DDIM (eta = 0) as installed by the benchmark (BASELINE config 3: "50 DDIM steps")."""
@@ -138,6 +166,13 @@ class DDIMScheduler(_SchedulerBase):
         if eta > 0:
             prev = prev + std * randn_tensor(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
         return prev.to(sample.dtype)
+
+    def step_coeffs(self, t, eta=0.0):
+        """`step()` at timestep t as StepCoeffs, from the same `.item()` floats; noise is drawn only when eta > 0."""
+        a_t, a_prev = self.alphas_for(t)
+        var = (1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)
+        std = eta * var**0.5
+        return StepCoeffs(a_t**0.5, (1 - a_t) ** 0.5, a_prev**0.5, max(1 - a_prev - std**2, 0.0) ** 0.5, 0.0, std, eta > 0)
 
     def step_cfg_fused_(self, noise_pred_nhwc, t, latents_nhwc, next_in, guidance_scale):
         """CFG combine + eta=0 update + next UNet input in ONE kernel (in place on the fp32 NHWC latents)."""

@@ -257,6 +257,14 @@ int dllm_reduce_sum_f32(const float* in, int64_t n, float* out, void* stream);  
  * next_in bf16 [2B,P,8] (channel-padded conv_in operand) or NULL. */
 int dllm_cfg_ddim_step(const void* pred, float* latents, void* next_in, int64_t n_half, int64_t unused, float guidance,
                        float sqrt_at, float sqrt_1mat, float sqrt_aprev, float sqrt_1maprev, int v_prediction, void* stream);
+/* Any scheduler's step as coefficients (csrc/denoise.hip; schedulers.py `step_coeffs`), with or without CFG and with guidance
+ * rescale (modeling_plugins.py:658-669, 824-833): pred bf16 [G*B,P,4] NHWC (G = 2: uncond half first; G = 1: no CFG), latents fp32
+ * [B,P,4] in place, noise fp32 [B,P,4] (read only when sigma != 0, else may be NULL), next_in bf16 [G*B,P,8] or NULL.
+ * e = e_u + guidance (e_c - e_u); rescale > 0: e = rescale e std(e_c)/std(e) + (1 - rescale) e (unbiased, per image);
+ * x0 / eps from e (v_prediction or epsilon); x_prev = k_x0 x0 + k_eps eps + k_x x + sigma noise.  Deterministic: no atomics. */
+int dllm_cfg_sched_step(const void* pred, float* latents, const float* noise, void* next_in, int64_t B, int64_t P, int G,
+                        float guidance, float rescale, int v_prediction, float sqrt_at, float sqrt_1mat, float k_x0, float k_eps,
+                        float k_x, float sigma, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------- greedy decode
  * Token step of the KV-cache decode loop (omni/eval/language_eval/modeling_dreamllm.py:76-97): every nn.Linear of
