@@ -1646,6 +1646,86 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
         return ops.beam_finalize(state, n, input_ids, nrs, max_length, eos, pad, length_penalty)
 
     @torch.no_grad()
+    def loglikelihood(self, requests, *, vocab_limit=None, max_batch_tokens=8192, max_batch_rows=64, return_token_logprobs=False):
+        """log p(continuation | context) of given text: what the reference's multiple-choice scorers compute per answer choice
+        (omni/eval/language_eval/submission_scripts/submission_dev_{hellaswag,piqa,siqa,boolq,winogrande}.py: `model(cat(question,
+        ending))`, `log_softmax(logits.cpu().float())`, `gather` at rows [-n-1:-1]), for any number of requests at once.
+
+        `requests`: (context_ids, continuation_ids) pairs (lists or 1-D LongTensors; the context holds at least one token, usually
+        from bos on).  They are sorted by length and cut into right-padded ragged batches (`scoring.plan_batches`: at most
+        `max_batch_rows` rows and `max_batch_tokens` padded tokens each); every batch is ONE decoder forward with `seqlens=`, then
+        lm_head runs on the scored rows only, a chunk at a time, into the scoring kernel (`ops.lm_head_score`): the [B, S, V]
+        logits are never formed and nothing is copied to the host inside a batch.  `vocab_limit` (e.g. 32000, the reference's
+        `logits[..., :32000]`) restricts the softmax and the arg-max to the ids below it.
+
+        -> `LoglikelihoodOutput(sum_logprob fp32 [N], num_tokens int64 [N], is_greedy bool [N], token_logprobs)` in request order
+        on the model's device; `token_logprobs` is a list of N fp32 tensors with `return_token_logprobs`, else None.  A row with a
+        NaN / infinite logit (or a target outside the vocabulary limit, which the request check rules out) raises FloatingPointError
+        after the last batch, naming the first request whose sum is not finite.
+
+        Rolling perplexity of a document is the same call: `loglikelihood([(ids[:1], ids[1:])])`, perplexity =
+        exp(-sum_logprob / num_tokens)."""
+        from . import scoring
+        V = self.lm_head.weight.shape[0]
+        lim = V if vocab_limit is None else min(int(vocab_limit), V)
+        batches, restore = scoring.plan_batches(requests, max_batch_tokens, max_batch_rows, max_len=self.config.max_position_embeddings,
+                                                vocab=lim)
+        dev = self.lm_head.weight.device
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        sums, greedy, counts, tokens = [], [], [], []
+        for b in batches:
+            ids = b.input_ids.to(dev)
+            hs = self.model(input_ids=ids, seqlens=b.seqlens.to(dev), use_cache=False, return_dict=True).last_hidden_state
+            sc = ops.lm_head_score(hs.reshape(-1, hs.shape[-1]), self.lm_head.weight, b.rows.to(dev), b.targets.to(dev),
+                                   vocab_limit=lim, seg_start=b.seg_start.to(dev), status=status)
+            sums.append(sc.sum_logprob)
+            greedy.append(sc.all_greedy)
+            n = b.seg_start[1:] - b.seg_start[:-1]   # (host tensors of the plan: no sync)
+            counts.append(n)
+            if return_token_logprobs:
+                tokens.extend(torch.split(sc.logprob, n.tolist()))
+        restore_d = restore.to(dev)
+        if not batches:
+            return scoring.LoglikelihoodOutput(torch.zeros(0, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
+                                               torch.zeros(0, dtype=torch.bool, device=dev), [] if return_token_logprobs else None)
+        out = scoring.LoglikelihoodOutput(torch.cat(sums)[restore_d], torch.cat(counts).to(dev)[restore_d], torch.cat(greedy)[restore_d],
+                                          [tokens[i] for i in restore.tolist()] if return_token_logprobs else None)
+        st = int(status.item())
+        if st != 0:
+            bad = (~torch.isfinite(out.sum_logprob)).nonzero().flatten().tolist()
+            raise FloatingPointError(f"loglikelihood: the scoring kernel reported status {st} (1: a target outside the vocabulary limit, "
+                                     f"2: a row of logits with a NaN or an infinity); first request whose sum_logprob is not finite: "
+                                     f"{'request ' + str(bad[0]) if bad else 'none'}")
+        return out
+
+    @torch.no_grad()
+    def choice_logprobs(self, input_ids, candidate_ids, attention_mask=None, vocab_limit=None):
+        """Log-probabilities of up to 16 candidate next tokens at each row's LAST VALID token, and that row's arg-max: the MMLU call
+        (omni/eval/language_eval/eval_mmlu.py:43-62, evaluate_mmlu.py:62-87 read `logits[:, -1]` at the ids of "A", "B", "C", "D";
+        their softmax over the four numbers stays with the caller).  `input_ids` [B, S] with an optional left- or right-padding
+        `attention_mask`; `candidate_ids`: K <= 16 ids shared by all rows.  -> (cand_logprob fp32 [B, K] = log_softmax over the ids
+        below `vocab_limit` at the candidates, argmax int64 [B]).  lm_head runs on those B rows only."""
+        cands = [int(c) for c in (candidate_ids.tolist() if torch.is_tensor(candidate_ids) else candidate_ids)]
+        if not 0 < len(cands) <= ops.SCORE_MAX_CAND:
+            raise ValueError(f"choice_logprobs: between 1 and {ops.SCORE_MAX_CAND} candidate ids, got {len(cands)}")
+        B, S = input_ids.shape
+        dev = self.lm_head.weight.device
+        input_ids = input_ids.to(dev)
+        last = torch.full((B,), S - 1, dtype=torch.int64, device=dev)
+        if attention_mask is not None:
+            attention_mask = attention_mask.to(dev)
+            start, lens = _mask_to_spans(attention_mask)
+            if lens is not None:
+                if bool((lens <= 0).any()):
+                    raise ValueError("choice_logprobs: a row of attention_mask has no valid token")
+                last = (lens if start is None else start + lens).long() - 1
+        hs = self.model(input_ids=input_ids, attention_mask=attention_mask, use_cache=False, return_dict=True).last_hidden_state
+        rows = torch.arange(B, device=dev) * S + last
+        sc = ops.lm_head_score(hs.reshape(-1, hs.shape[-1]), self.lm_head.weight, rows, torch.full((B,), -1, dtype=torch.int64, device=dev),
+                               vocab_limit=vocab_limit, cand_ids=cands)
+        return sc.cand_logprob, sc.argmax
+
+    @torch.no_grad()
     def get_prompt_embeds(self, input_ids, attention_mask=None, images=None):
         """Prompt -> dream-query hidden states (modeling_dreamllm.py:1598-1672): prefill the text with a KV cache, then run
         [<dream_start>, 64 queries, <dream_end>] against it with the mask `cat([text_mask, ones])` (:1656-1657) and take the

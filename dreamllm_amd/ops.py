@@ -5,6 +5,7 @@ kernel.  There is NO eager fallback -- a CPU tensor or a missing library raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 import os
@@ -1289,6 +1290,133 @@ def lm_head_ce(hidden2d, weight, labels1d, return_logits=False, rows=None):
         hidden2d = gather_rows_unique(hidden2d, rows)   # backward: scatter into a zero [T, d]
         labels1d = labels1d[rows]
     return LMHeadCEFn.apply(hidden2d, weight, labels1d, torch.is_grad_enabled())
+
+
+# --------------------------------------------------------------------------------------------- scoring of given text
+SCORE_MAX_CAND = 16
+SCORE_TARGET_OUT_OF_RANGE, SCORE_ROW_NOT_FINITE = 1, 2   # bits of the `status` word (csrc/score.hip)
+
+ScoreRows = collections.namedtuple("ScoreRows", "logprob argmax greedy lse rank cand_logprob status")
+ScoreSegments = collections.namedtuple("ScoreSegments", "sum_logprob all_greedy")
+HeadScore = collections.namedtuple("HeadScore", "logprob argmax greedy lse rank cand_logprob status sum_logprob all_greedy")
+
+
+def _score_vocab(C, vocab_limit):
+    V = C if vocab_limit is None else min(int(vocab_limit), C)
+    if V <= 0:
+        raise ValueError(f"vocabulary limit {vocab_limit} leaves no id to score")
+    return V
+
+
+def _score_cand(cand_ids, V, device):
+    """Candidate ids (a sequence of ints or a CPU / device LongTensor) -> int64 [K] on `device`, checked against [0, V) on the host."""
+    if cand_ids is None:
+        return None, 0
+    ids = [int(c) for c in (cand_ids.tolist() if isinstance(cand_ids, torch.Tensor) else cand_ids)]
+    if not 0 < len(ids) <= SCORE_MAX_CAND:
+        raise ValueError(f"between 1 and {SCORE_MAX_CAND} candidate ids, got {len(ids)}")
+    bad = [c for c in ids if not 0 <= c < V]
+    if bad:
+        raise ValueError(f"candidate ids {bad} outside [0, {V})")
+    return torch.tensor(ids, dtype=torch.int64, device=device), len(ids)
+
+
+class _CheckedCand(tuple):
+    """(device ids, K) that `_score_cand` has already checked against the same limit: `lm_head_score` checks and uploads once, not per chunk."""
+
+
+def score_rows(logits, targets, *, vocab_limit=None, cand_ids=None, want_lse=False, want_rank=False, status=None):
+    """Per row of fp32 `logits` [R, C] with target id `targets[r]` (int64 [R]; < 0: row not scored), over the ids below `vocab_limit`
+    (None: C) in one launch (`dllm_score_rows`, semantics in csrc/score.hip) -> `ScoreRows` of device tensors: logprob fp32 [R]
+    (log_softmax at the target), argmax int64 [R] (lowest id of the maximum), greedy bool [R] (argmax == target), lse fp32 [R]
+    (`want_lse`) , rank int32 [R] (`want_rank`: number of ids ahead of the target, 0 <=> greedy), cand_logprob fp32 [R, K] for up to 16
+    `cand_ids` shared by all rows, status int32 [1] (bit 0: a target >= the limit, bit 1: a row with a NaN / +inf; OR-ed into `status`
+    if one is passed, so that several launches share one word)."""
+    _need_gpu(logits, targets)
+    if logits.dtype != torch.float32:
+        raise TypeError("score_rows expects fp32 logits (reference: logits.float())")
+    if logits.dim() != 2 or targets.dim() != 1 or targets.numel() != logits.shape[0] or targets.dtype != torch.int64:
+        raise ValueError("score_rows: logits [R, C] and int64 targets [R]")
+    R, C = logits.shape
+    V = _score_vocab(C, vocab_limit)
+    dev = logits.device
+    if logits.stride(1) != 1 or logits.stride(0) % 4 or logits.data_ptr() % 16 or (R > 1 and logits.stride(0) < V):
+        buf = torch.empty(R, (V + 3) // 4 * 4, dtype=torch.float32, device=dev)   # 16-byte rows for the kernel's vector loads
+        buf[:, :V].copy_(logits[:, :V])
+        logits = buf
+    cand, K = cand_ids if isinstance(cand_ids, _CheckedCand) else _score_cand(cand_ids, V, dev)
+    targets = targets.contiguous()
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
+        raise TypeError("score_rows: status must be an int32 tensor on the logits' device")
+    logprob = torch.empty(R, dtype=torch.float32, device=dev)
+    argmax = torch.empty(R, dtype=torch.int64, device=dev)
+    greedy = torch.empty(R, dtype=torch.bool, device=dev)
+    lse = torch.empty(R, dtype=torch.float32, device=dev) if want_lse else None
+    rank = torch.empty(R, dtype=torch.int32, device=dev) if want_rank else None
+    cand_lp = torch.empty(R, K, dtype=torch.float32, device=dev) if K else None
+    check("dllm_score_rows", _p(logits), max(logits.stride(0), (V + 3) // 4 * 4), R, V, _p(targets), _p(logprob), _p(lse), _p(argmax),
+          _p(greedy), _p(rank), _p(cand), K, _p(cand_lp), _p(status), _stream())
+    return ScoreRows(logprob, argmax, greedy, lse, rank, cand_lp, status)
+
+
+def score_segments(logprob, greedy, seg_start):
+    """Totals per request of `score_rows`' outputs (`dllm_score_segments`): for the rows [seg_start[n], seg_start[n + 1]) (int64 [N + 1],
+    ascending) -> sum_logprob fp32 [N] (added in row order: the bits do not depend on N) and all_greedy bool [N]."""
+    _need_gpu(logprob, greedy, seg_start)
+    if logprob.dtype != torch.float32 or greedy.dtype != torch.bool or seg_start.dtype != torch.int64 or seg_start.numel() < 1:
+        raise TypeError("score_segments: fp32 logprob [R], bool greedy [R], int64 seg_start [N + 1]")
+    logprob, greedy, seg_start = logprob.contiguous(), greedy.contiguous(), seg_start.contiguous()
+    if greedy.numel() != logprob.numel():
+        raise ValueError("score_segments: logprob and greedy differ in length")
+    N = seg_start.numel() - 1
+    total = torch.empty(N, dtype=torch.float32, device=logprob.device)
+    allg = torch.empty(N, dtype=torch.bool, device=logprob.device)
+    check("dllm_score_segments", _p(logprob), _p(greedy), _p(seg_start), N, logprob.numel(), _p(total), _p(allg), _stream())
+    return ScoreSegments(total, allg)
+
+
+@torch.no_grad()
+def lm_head_score(hidden2d, weight, rows, targets, *, vocab_limit=None, cand_ids=None, seg_start=None, want_lse=False, want_rank=False,
+                  status=None):
+    """lm_head + `score_rows` on ONLY the rows that are scored, never holding more than one chunk of logits: `rows` (int64 [R], flat
+    row indices into the bf16 hidden states [T, d]) are gathered, then per chunk of LM_HEAD_CE_CHUNK_ROWS rows the fp32 logits chunk
+    (the same GEMM on the same zero-padded weight as the fused lm_head + CE) goes straight into the scoring kernel.  `targets` int64
+    [R]; `seg_start` int64 [N + 1] adds the per-request totals.  -> `HeadScore`.  Inference only: no autograd function."""
+    _need_gpu(hidden2d, weight, rows, targets)
+    _bf16(hidden2d, weight)
+    if hidden2d.dim() != 2 or rows.dim() != 1 or targets.shape != rows.shape or targets.dtype != torch.int64 or rows.dtype != torch.int64:
+        raise ValueError("lm_head_score: hidden [T, d], int64 rows [R] and int64 targets [R]")
+    dev = hidden2d.device
+    R = rows.numel()
+    V = _score_vocab(weight.shape[0], vocab_limit)
+    cand = _CheckedCand(_score_cand(cand_ids, V, dev))   # checked and uploaded once here, not per chunk
+    K = cand[1]
+    h = gather_rows(hidden2d, rows)
+    wp = _pad_vocab(weight)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    logprob = torch.empty(R, dtype=torch.float32, device=dev)
+    argmax = torch.empty(R, dtype=torch.int64, device=dev)
+    greedy = torch.empty(R, dtype=torch.bool, device=dev)
+    lse = torch.empty(R, dtype=torch.float32, device=dev) if want_lse else None
+    rank = torch.empty(R, dtype=torch.int32, device=dev) if want_rank else None
+    cand_lp = torch.empty(R, K, dtype=torch.float32, device=dev) if K else None
+    C = max(256, int(LM_HEAD_CE_CHUNK_ROWS))
+    for r0 in range(0, R, C):
+        r1 = min(R, r0 + C)
+        logits_c = linear_fwd(h[r0:r1], wp, out_dtype=torch.float32)
+        sc = score_rows(logits_c[:, :V], targets[r0:r1], cand_ids=cand, want_lse=want_lse, want_rank=want_rank, status=status)
+        del logits_c
+        logprob[r0:r1], argmax[r0:r1], greedy[r0:r1] = sc.logprob, sc.argmax, sc.greedy
+        for dst, src in ((lse, sc.lse), (rank, sc.rank), (cand_lp, sc.cand_logprob)):
+            if dst is not None:
+                dst[r0:r1] = src
+    total = allg = None
+    if seg_start is not None:
+        total, allg = score_segments(logprob, greedy, seg_start)
+    return HeadScore(logprob, argmax, greedy, lse, rank, cand_lp, status, total, allg)
 
 
 # --------------------------------------------------------------------------------------------- UNet operators (NHWC)

@@ -319,6 +319,24 @@ int dllm_beam_step(const float* logits, int64_t ld, int B, int nb, int V, float*
                    int* hyp_count, double* worst, int* done, int64_t eos, int64_t pad, int64_t length_penalty_bits,
                    int early_stopping, int max_new, int len_offset, const int* kv_len, int* row_map, int64_t map_ld,
                    float* cand_score, int* cand_flat, int* status, void* stream);
+/* Scoring of given text (csrc/score.hip; omni/eval/language_eval/submission_scripts/submission_dev_*.py `log_softmax` + `gather` at
+ * rows [-n-1:-1], eval_mmlu.py:43-62 `logits[:, -1]` at four ids; rules in INTEGRATION.md "Scoring").  One block per row of fp32 logits
+ * [rows][ld] (ld a multiple of 4, logits 16-byte aligned), the ids i < V considered, t = targets[r]:  logprob[r] = (x_t - max) -
+ * log sum exp(x - max); lse[r] (optional) = max + log sum exp(x - max); argmax[r] = the lowest id of the maximum; greedy[r] (uint8) =
+ * argmax == t; rank[r] (optional) = #(x_i > x_t) + #(i < t: x_i == x_t); cand_logprob[r][k] = x_{cand_ids[k]} - lse for n_cand <= 16
+ * ids shared by all rows (a candidate id outside [0, V): NaN).  t < 0 (row not scored): logprob 0, greedy 0, rank -1, the other outputs
+ * as usual.  t >= V: logprob -inf, greedy 0, rank -1, *status |= 1.  A row with a NaN or +inf, or without a finite value: lse and
+ * candidates NaN, argmax 0, greedy 0, rank -1, logprob NaN for a target in [0, V), *status |= 2.  status (int32, optional) is only
+ * ever OR-ed into.  Each row is read once (V <= 32768: kept in registers; larger V re-reads it).  Deterministic: fixed-order sums, no
+ * float atomics. */
+int dllm_score_rows(const float* logits, int64_t ld, int64_t rows, int V, const int64_t* targets, float* logprob, float* lse,
+                    int64_t* argmax, void* greedy, int* rank, const int64_t* cand_ids, int n_cand, float* cand_logprob, int* status,
+                    void* stream);
+/* Per-request totals of dllm_score_rows' outputs: for n < n_seg over rows [seg_start[n], seg_start[n + 1]) (int64, ascending, clamped
+ * to [0, rows]): sum_logprob[n] = the logprob values added one after the other in row order from 0 (one wave per segment: the bits
+ * depend on the segment alone), all_greedy[n] (uint8) = every greedy flag of the segment is set (1 for an empty segment). */
+int dllm_score_segments(const float* logprob, const void* greedy, const int64_t* seg_start, int64_t n_seg, int64_t rows,
+                        float* sum_logprob, void* all_greedy, void* stream);
 int64_t dllm_attn_decode_ws_floats(int B, int H, int D, int nsplit);
 /* row_map (int32 [B][map_ld] on device, or NULL; here and in dllm_attn_decode_rope): beam search's copy-free KV cache -- key slot j
  * of sequence b is read from cache row row_map[b * map_ld + j] (an entry outside [0, B) reads row b); a separate kernel
