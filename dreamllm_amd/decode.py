@@ -8,11 +8,14 @@ stream.  Here the token step is a fixed sequence of launches on static buffers:
     embed[tok] -> 32 x { [RMSNorm + q/k/v GEMV] -> [RoPE(pos on device) + K/V append to the cache at pos] -> decode attention
     over the cache (valid length on device) -> [o GEMV + residual] -> [RMSNorm + gate/up GEMV + SwiGLU] -> [down GEMV + residual] }
     -> [final RMSNorm + lm_head GEMV] (fp32 logits) -> argmax -> pos/len/step += 1      ([..] = one launch; 7 per layer;
-    round 4: RoPE + append folded into the attention launch -> 6 per layer; the split-KV merge can be folded in
-    too (`fuse_combine=True`: 5 per layer) but measured 1 % slower than the separate combine launch)
+    round 4: RoPE + append folded into the attention launch -> 6 per layer)
 
-captured once per (batch, max_len) in a hipGraph (`torch.cuda.CUDAGraph`) and replayed per token; nothing in it depends on the
-host.  Prefill runs through the normal model forward (MFMA GEMMs + flash attention) and its K/V are copied into the cache.
+The two 5-launch forms (the split-KV merge inside the attention launch, or inside the o projection's GEMV) were built and measured
+slower than the separate combine launch (DESIGN.md "Decode"; 298.6 against 308.3 tok/s, profiles/r06_decode_merge_ab.log); their
+kernels and launchers stay in `ops` with their unit tests, the session no longer exposes them.
+
+The step is captured once per (batch, max_len) in a hipGraph (`torch.cuda.CUDAGraph`) and replayed per token; nothing in it depends
+on the host.  Prefill runs through the normal model forward (MFMA GEMMs + flash attention) and its K/V are copied into the cache.
 """
 from __future__ import annotations
 
@@ -21,26 +24,19 @@ import math
 import torch
 
 from . import ops
+from .generation import check_left_padded, left_pad_position_ids
 
 
 class GreedyDecodeSession:
     def __init__(self, model, batch_size: int, max_len: int, use_graph: bool = True, nsplit: int = 8, fused: bool = True,
-                 vocab_limit: int | None = 32000, fuse_rope: bool = True, fuse_combine: bool = False, merge_in_oproj: bool = False):
+                 vocab_limit: int | None = 32000):
         """`vocab_limit`: argmax runs over `logits[..., :vocab_limit]` -- the reference loop slices `[..., :32000]`
         (omni/eval/language_eval/modeling_dreamllm.py:79,86) so that none of the added special tokens (<dream_start>, <im_*>,
-        [PAD] ...) can be emitted; None = whole vocabulary."""
+        [PAD] ...) can be emitted; None = whole vocabulary.  `fused=False`: the token step one launch per operation, the
+        reference form of the fused step in the tests."""
         cfg = model.config
         self.model = model
         self.B, self.max_len, self.use_graph, self.nsplit, self.fused = batch_size, max_len, use_graph, nsplit, fused
-        self.fuse_rope = fuse_rope
-        # round 6 (opt-in, measured SLOWER: 298.6 against 308.3 tok/s in one process, profiles/r06_decode_merge_ab.log): the o projection's GEMV
-        # merges the split-KV partials itself while staging x (5 launches per layer instead of 6) -- each of its ~512 blocks then re-reads the
-        # 133 KB of partials from L2, which costs more than the 5.5 us combine launch it removes; LDS staging covers up to 4 sequences
-        self.merge_oproj = bool(merge_in_oproj) and fuse_rope and fused and batch_size <= 4 and \
-            batch_size * cfg.hidden_size * 2 <= 60 * 1024
-        # arrival counters of the in-launch split-KV merge (zero at rest; one array per session = per stream in flight)
-        self.attn_counters = (torch.zeros(batch_size * cfg.num_attention_heads, dtype=torch.int32, device=model.device)
-                              if fuse_combine else None)
         if batch_size > 8:
             raise ValueError("the decode GEMV handles up to 8 sequences per step")
         dev, dt = model.device, model.dtype
@@ -78,31 +74,13 @@ class GreedyDecodeSession:
         for li, layer in enumerate(m.model.layers):
             at, mlp = layer.self_attn, layer.mlp
             if self.fused:
-                # 7 launches per layer: [RMSNorm + q/k/v GEMV] [RoPE + cache append] [attention x2] [o GEMV + residual]
+                # 6 launches per layer: [RMSNorm + q/k/v GEMV] [RoPE + cache append + attention x2] [o GEMV + residual]
                 # [RMSNorm + gate/up GEMV + SwiGLU] [down GEMV + residual]
                 q, k, v = ops.gemv_fused(x, (at.q_proj.weight, at.k_proj.weight, at.v_proj.weight),
                                          norm_w=layer.input_layernorm.weight, eps=eps)
-                q = q.view(B, H, D)
-                if self.merge_oproj:
-                    # round 6: 5 launches per layer -- the split-KV partials go straight into the o projection, whose blocks merge them
-                    # while staging x (no combine launch)
-                    ws = ops.attn_decode_rope(q, k.view(B, Hkv, D), v.view(B, Hkv, D), self.kc[li], self.vc[li], self.kv_len, self.cos,
-                                              self.sin, pos, 1.0 / math.sqrt(D), self.nsplit, kv_start=self.kv_start, partials_only=True,
-                                              row_map=self.row_map)
-                    x2 = ops.gemv_attn_combine(ws, at.o_proj.weight, B, H, D, self.nsplit, residual=x)
-                    act = ops.gemv_fused(x2, (mlp.gate_proj.weight, mlp.up_proj.weight), norm_w=layer.post_attention_layernorm.weight,
-                                         eps=eps, swiglu=True)
-                    x = ops.gemv(act, mlp.down_proj.weight, residual=x2)
-                    continue
-                if self.fuse_rope:   # RoPE + cache append inside the attention launch (round 4)
-                    o = ops.attn_decode_rope(q, k.view(B, Hkv, D), v.view(B, Hkv, D), self.kc[li], self.vc[li], self.kv_len, self.cos,
-                                             self.sin, pos, 1.0 / math.sqrt(D), self.nsplit, kv_start=self.kv_start,
-                                             counters=self.attn_counters, row_map=self.row_map)
-                else:
-                    ops.rope_append_(q, k.view(B, Hkv, D), v.view(B, Hkv, D), self.kc[li], self.vc[li], self.cos, self.sin, pos,
-                                     kv_len=self.kv_len)
-                    o = ops.attn_decode(q, self.kc[li], self.vc[li], self.kv_len, 1.0 / math.sqrt(D), self.nsplit,
-                                        kv_start=self.kv_start, row_map=self.row_map)
+                o = ops.attn_decode_rope(q.view(B, H, D), k.view(B, Hkv, D), v.view(B, Hkv, D), self.kc[li], self.vc[li], self.kv_len,
+                                         self.cos, self.sin, pos, 1.0 / math.sqrt(D), self.nsplit, kv_start=self.kv_start,
+                                         row_map=self.row_map)
                 x2 = ops.gemv(o.view(B, H * D), at.o_proj.weight, residual=x)
                 act = ops.gemv_fused(x2, (mlp.gate_proj.weight, mlp.up_proj.weight), norm_w=layer.post_attention_layernorm.weight,
                                      eps=eps, swiglu=True)
@@ -153,40 +131,53 @@ class GreedyDecodeSession:
         """Device state a token step changes (saved around the warm-up step before capture)."""
         return (self.tok, self.pos, self.kv_len, self.slot, self.step_idx, self.out_tokens)
 
-    # ---- public ----------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def prefill(self, input_ids, images=None, attention_mask=None, forced_tokens=None, forced_mask=None):
-        """Run the prompt through the model (MFMA path), fill the cache, emit the first new token.
+    def _prefill_prompt(self, input_ids, images, attention_mask, rows=1):
+        """Prompt [B, S] through the model (MFMA path), its K/V into cache rows b * rows, and the step state of all B * rows session
+        rows set for the first token step.  -> last-position logits [B, V]; the caller chooses the first token from them.
 
         `attention_mask` (LEFT padding, the layout of the reference's batched generate() callers,
-        omni/eval/vqa/vqa_inference.py:276): position ids are mask-aware as HF generate computes them
-        (`prepare_inputs_for_generation`, modeling_dreamllm.py:1527-1533); every row's next token goes to cache slot S, its
-        position is the row's own length, and the pad slots in front are masked in the token steps (`kv_start`).  Right-padded
-        or holey masks raise: a right-padded row would need a hole between its prompt and its new tokens.
-        `forced_tokens` / `forced_mask` [B, n]: token i after the prompt is forced to `forced_tokens[:, i]` where
-        `forced_mask[:, i]` is set (teacher forcing of rows still inside their prompt, reference loop :93-94)."""
+        omni/eval/vqa/vqa_inference.py:276): position ids are mask-aware as HF generate computes them; every row's next token goes
+        to cache slot S, its position is the row's own length, and the pad slots in front are masked in the token steps
+        (`kv_start`).  Right-padded or holey masks raise (`check_left_padded`)."""
         B, S = input_ids.shape
-        if B != self.B or S >= self.max_len:
-            raise ValueError(f"prompt [{B},{S}] does not fit the session (batch {self.B}, max_len {self.max_len})")
+        if B * rows != self.B or S >= self.max_len:
+            raise ValueError(f"prompt [{B},{S}] does not fit the session (batch {self.B // rows}, max_len {self.max_len})")
         dev = self.tok.device
-        position_ids, lens = None, None
+        position_ids = None
+
+        def per_row(t):  # [B] -> [B * rows]
+            return t.repeat_interleave(rows) if rows > 1 else t
+
         if attention_mask is not None:
             am = attention_mask.to(dev) != 0
-            lens = am.sum(-1)
-            start = S - lens
-            left = torch.arange(S, device=dev)[None] >= start[:, None]
-            if not bool((left == am).all()):
-                raise ValueError("GreedyDecodeSession.prefill: attention_mask must be LEFT-padded (one run of valid tokens ending "
-                                 "at the last prompt position); use forced_tokens for right-padded ragged prompts")
-            position_ids = (am.long().cumsum(-1) - 1).masked_fill(~am, 1)
-            self.kv_start.copy_(start.to(torch.int32))
+            start, lens = check_left_padded(am, type(self).__name__ + ".prefill")
+            position_ids = left_pad_position_ids(am)
+            self.kv_start.copy_(per_row(start.to(torch.int32)))
+            self.pos.copy_(per_row(lens)[:, None])
         else:
             self.kv_start.zero_()
+            self.pos.fill_(S)
         out = self.model(input_ids=input_ids, images=images, attention_mask=attention_mask, position_ids=position_ids,
                          use_cache=True, return_dict=True)
         for li, (k, v) in enumerate(out.past_key_values):  # reference layout [B, Hkv, S, D]
-            self.kc[li][:, :S].copy_(k.transpose(1, 2))
-            self.vc[li][:, :S].copy_(v.transpose(1, 2))
+            self.kc[li][::rows, :S].copy_(k.transpose(1, 2))
+            self.vc[li][::rows, :S].copy_(v.transpose(1, 2))
+        self.kv_len.fill_(S + 1)
+        self.slot.copy_(torch.arange(self.B, device=dev) * self.max_len + S)
+        self.step_idx.zero_()
+        self.prompt_len = S
+        self.generated = 0  # tokens produced by generate() since this prefill (host-side count of graph replays)
+        return out.logits[:, -1]
+
+    # ---- public ----------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def prefill(self, input_ids, images=None, attention_mask=None, forced_tokens=None, forced_mask=None):
+        """Run the prompt through the model, fill the cache (`_prefill_prompt`), emit the first new token.
+
+        `forced_tokens` / `forced_mask` [B, n]: token i after the prompt is forced to `forced_tokens[:, i]` where
+        `forced_mask[:, i]` is set (teacher forcing of rows still inside their prompt, reference loop :93-94)."""
+        logits = self._prefill_prompt(input_ids, images, attention_mask)
+        dev = self.tok.device
         self.force_mask.zero_()
         f_tok = f_mask = None
         if forced_tokens is not None:
@@ -195,18 +186,8 @@ class GreedyDecodeSession:
                 f_tok, f_mask = forced_tokens[:, 0].to(dev), forced_mask[:, 0].to(dev)
                 self.force_tok[: n - 1].copy_(forced_tokens[:, 1:].t())
                 self.force_mask[: n - 1].copy_(forced_mask[:, 1:].t())
-        self.step_idx.zero_()
-        first = self._choose_first(out.logits[:, -1], f_tok, f_mask)
+        first = self._choose_first(logits, f_tok, f_mask)
         self.tok.copy_(first)
-        if lens is None:
-            self.pos.fill_(S)
-        else:
-            self.pos.copy_(lens[:, None])
-        self.kv_len.fill_(S + 1)
-        self.slot.copy_(torch.arange(B, device=dev) * self.max_len + S)
-        self.prompt_len = S
-        self.generated = 0  # tokens produced by generate() since this prefill (host-side count of graph replays)
-        self.first = first
         return first
 
     @torch.no_grad()
@@ -340,39 +321,14 @@ class BeamDecodeSession(GreedyDecodeSession):
     def prefill(self, input_ids, images=None, attention_mask=None):
         """Prompt [B, S] (LEFT-padded with `attention_mask`) through the model once per batch; its K/V go to row b * nb, every beam's
         map points there; then beam step 0 from the last-position logits.  Returns the step's tokens [B * nb]."""
-        B, S = input_ids.shape
         nb, R = self.nb, self.B
-        if B != self.nbatch or S >= self.max_len:
-            raise ValueError(f"prompt [{B},{S}] does not fit the session (batch {self.nbatch}, max_len {self.max_len})")
-        dev = self.tok.device
-        position_ids, lens = None, None
-        if attention_mask is not None:
-            am = attention_mask.to(dev) != 0
-            lens = am.sum(-1)
-            start = S - lens
-            if not bool(((torch.arange(S, device=dev)[None] >= start[:, None]) == am).all()):
-                raise ValueError("BeamDecodeSession.prefill: attention_mask must be LEFT-padded")
-            position_ids = (am.long().cumsum(-1) - 1).masked_fill(~am, 1)
-            self.kv_start.copy_(start.to(torch.int32).repeat_interleave(nb))
-        else:
-            self.kv_start.zero_()
-        out = self.model(input_ids=input_ids, images=images, attention_mask=attention_mask, position_ids=position_ids,
-                         use_cache=True, return_dict=True)
-        for li, (k, v) in enumerate(out.past_key_values):  # reference layout [B, Hkv, S, D]
-            self.kc[li][::nb, :S].copy_(k.transpose(1, 2))
-            self.vc[li][::nb, :S].copy_(v.transpose(1, 2))
-        rows = torch.arange(R, device=dev, dtype=torch.int32)
+        logits = self._prefill_prompt(input_ids, images, attention_mask, rows=nb)
+        rows = torch.arange(R, device=self.tok.device, dtype=torch.int32)
         self.row_map.copy_((rows // nb * nb)[:, None].expand(R, self.max_len))
-        self.row_map[:, S] = rows
+        self.row_map[:, self.prompt_len] = rows
         self.beam.reset()
         self.beam.status.zero_()
-        self.first_logits = out.logits[:, -1].float().repeat_interleave(nb, 0)
+        self.first_logits = logits.float().repeat_interleave(nb, 0)
         ops.beam_step(self.first_logits, self.beam, eos=self.eos, pad=self.pad, length_penalty=self.length_penalty,
                       early_stopping=self.early_stopping, max_new=self.max_new)
-        self.pos.copy_((torch.full((B,), S, device=dev) if lens is None else lens).repeat_interleave(nb)[:, None])
-        self.kv_len.fill_(S + 1)
-        self.slot.copy_(torch.arange(R, device=dev) * self.max_len + S)
-        self.step_idx.zero_()
-        self.prompt_len = S
-        self.generated = 0
         return self.tok.clone()

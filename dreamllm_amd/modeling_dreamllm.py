@@ -1234,8 +1234,8 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
             input_ids = input_ids[:, -1:]
         position_ids = kwargs.get("position_ids", None)
         if attention_mask is not None and position_ids is None:
-            position_ids = attention_mask.long().cumsum(-1) - 1
-            position_ids.masked_fill_(attention_mask == 0, 1)
+            from .generation import left_pad_position_ids
+            position_ids = left_pad_position_ids(attention_mask)
             if past_key_values:
                 position_ids = position_ids[:, -1].unsqueeze(-1)
         if inputs_embeds is not None and past_key_values is None:
@@ -1263,69 +1263,9 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
         `attention_mask` selects HF-generate semantics (HF's greedy search does not slice).
         `fast` (default: batch <= 8) runs the token steps on the decode kernels (GEMV + cache attention, one hipGraph replay
         per token: `decode.GreedyDecodeSession`); `fast=False` re-enters the model forward per token like the reference."""
-        B, S = input_ids.shape
-        dev = input_ids.device
-        if vocab_limit == "auto":
-            vocab_limit = None if attention_mask is not None else 32000
-        V = min(int(vocab_limit), self.config.vocab_size) if vocab_limit is not None else self.config.vocab_size
-        if fast is None:
-            fast = B <= 8
-        tokens = forced = fmask = None
-        if pad_token_id is not None:
-            if attention_mask is not None:
-                raise ValueError("pass either pad_token_id (right-padded ragged prompts) or attention_mask (left-padded), not both")
-            text_mask = input_ids != pad_token_id
-            plen = text_mask.sum(-1)
-            if not bool((text_mask == (torch.arange(S, device=dev)[None] < plen[:, None])).all()):
-                raise ValueError("pad_token_id protocol: prompts must be right-padded")
-            s0 = int(plen.min())
-            total = S + max_new_tokens
-            tokens = torch.full((B, total), pad_token_id, dtype=torch.long, device=dev)
-            tokens[:, :S] = input_ids
-            fmask = torch.zeros(B, total, dtype=torch.bool, device=dev)
-            fmask[:, :S] = text_mask
-            forced, fm = tokens[:, s0:], fmask[:, s0:]
-            n_new = total - s0
-            prompt = input_ids[:, :s0]
-        else:
-            prompt, n_new, fm = input_ids, max_new_tokens, None
-        if fast:
-            from .decode import GreedyDecodeSession
-            key = (B, prompt.shape[1] + n_new + 1, use_graph, V)
-            sess = getattr(self, "_decode_session", None)
-            if sess is None or sess[0] != key:
-                sess = (key, GreedyDecodeSession(self, B, key[1], use_graph=use_graph, vocab_limit=V))
-                self._decode_session = sess
-            sess = sess[1]
-            first = sess.prefill(prompt, images=images, attention_mask=attention_mask, forced_tokens=forced, forced_mask=fm)
-            rest = sess.generate(n_new - 1)
-            new = torch.cat([first[:, None], rest], dim=1)
-        else:
-            position_ids = None
-            if attention_mask is not None:
-                position_ids = (attention_mask.long().cumsum(-1) - 1).masked_fill(attention_mask == 0, 1)
-            out = self(input_ids=prompt, images=images, attention_mask=attention_mask, position_ids=position_ids, use_cache=True,
-                       return_dict=True)
-            past, mask, new = out.past_key_values, attention_mask, []
-            for i in range(n_new):
-                nxt = out.logits[:, -1, :V].argmax(-1)
-                if fm is not None:
-                    nxt = torch.where(fm[:, i], forced[:, i], nxt)
-                new.append(nxt)
-                if i + 1 == n_new:
-                    break
-                pos = None
-                if mask is not None:
-                    mask = torch.cat([mask, mask.new_ones(B, 1)], dim=1)
-                    pos = (mask.long().sum(-1) - 1)[:, None]
-                out = self(input_ids=nxt[:, None], past_key_values=past, attention_mask=mask, position_ids=pos, use_cache=True,
-                           return_dict=True)
-                past = out.past_key_values
-            new = torch.stack(new, 1)
-        if tokens is not None:
-            tokens[:, s0:] = new
-            return tokens
-        return torch.cat([input_ids, new], dim=1)
+        from . import generation
+        return generation.greedy_decode(self, input_ids, max_new_tokens, images=images, fast=fast, use_graph=use_graph,
+                                        attention_mask=attention_mask, pad_token_id=pad_token_id, vocab_limit=vocab_limit)
 
     # transformers 4.35.2 GenerationConfig arguments `generate` does not implement, with the default value they may be passed at
     _GENERATE_UNSUPPORTED = {"num_beams": 1, "num_return_sequences": 1, "repetition_penalty": 1.0, "typical_p": 1.0,
@@ -1357,122 +1297,9 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
         if temperature == 0:
             return self.greedy_generate(input_ids, max_new_tokens, images=images, fast=fast, use_graph=use_graph,
                                         attention_mask=attention_mask, pad_token_id=pad_token_id, vocab_limit=vocab_limit)
-        if vocab_limit == "auto":
-            vocab_limit = None if attention_mask is not None else 32000
-        return self._sampled_decode(input_ids, max_new_tokens, float(temperature), int(top_k), float(top_p), vocab_limit, images,
-                                    attention_mask, pad_token_id, self._draw_seed(generator), fast, use_graph)[0]
-
-    def _sampled_decode(self, input_ids, max_new_tokens, temperature, top_k, top_p, vocab_limit, images, attention_mask,
-                        pad_token_id, seed, fast, use_graph, eos=None, pad=0, stopping_criteria=None, greedy=False):
-        """Shared body of `sample_generate` / `generate`.  Returns (tokens, number of new tokens before the trim).  `greedy`: u = 0
-        for every draw (with top-k 1: the first arg-max, as argmax picks it)."""
-        B, S = input_ids.shape
-        dev = input_ids.device
-        V = min(int(vocab_limit), self.config.vocab_size) if vocab_limit is not None else self.config.vocab_size
-        if fast is None:
-            fast = B <= 8
-        tokens = forced = fm = None
-        if pad_token_id is not None:
-            if attention_mask is not None:
-                raise ValueError("pass either pad_token_id (right-padded ragged prompts) or attention_mask (left-padded), not both")
-            text_mask = input_ids != pad_token_id
-            plen = text_mask.sum(-1)
-            if not bool((text_mask == (torch.arange(S, device=dev)[None] < plen[:, None])).all()):
-                raise ValueError("pad_token_id protocol: prompts must be right-padded")
-            s0 = int(plen.min())
-            total = S + max_new_tokens
-            tokens = torch.full((B, total), pad_token_id, dtype=torch.long, device=dev)
-            tokens[:, :S] = input_ids
-            fmask = torch.zeros(B, total, dtype=torch.bool, device=dev)
-            fmask[:, :S] = text_mask
-            forced, fm = tokens[:, s0:], fmask[:, s0:]
-            n_new = total - s0
-            prompt = input_ids[:, :s0]
-        else:
-            prompt, n_new = input_ids, max_new_tokens
-        eos = -1 if eos is None else int(eos)
-        crit = list(stopping_criteria or [])
-
-        def stop_after(new_so_far, scores):
-            ids = torch.cat([input_ids, new_so_far], 1)
-            for c in crit:
-                r = c(ids, scores)
-                if bool(r.all()) if isinstance(r, torch.Tensor) else bool(r):
-                    return True
-            return False
-
-        done = n_new
-        if fast:
-            from .decode import SampledDecodeSession
-            key = ("sample", B, prompt.shape[1] + n_new + 1, use_graph, V, temperature, top_k, top_p, eos, int(pad), greedy)
-            sess = getattr(self, "_decode_session", None)
-            if sess is None or sess[0] != key:
-                sess = (key, SampledDecodeSession(self, B, key[2], temperature, top_k, top_p, eos=eos, pad=pad, use_graph=use_graph,
-                                                  vocab_limit=V, fixed_u=0.0 if greedy else None))
-                self._decode_session = sess
-            sess = sess[1]
-            first = sess.prefill(prompt, images=images, attention_mask=attention_mask, forced_tokens=forced, forced_mask=fm, seed=seed)
-            parts = [first[:, None]]
-            n = 1
-            if crit and stop_after(first[:, None], sess.first_logits):
-                done = 1
-            elif eos >= 0 and bool(sess.finished.all()):
-                done = 1
-            else:
-                while n < n_new:
-                    m = 1 if crit else min(16, n_new - n)  # criteria see every token; eos alone is checked between chunks
-                    parts.append(sess.generate(m))
-                    n += m
-                    if crit and stop_after(torch.cat(parts, 1), sess.logits):
-                        done = n
-                        break
-                    if eos >= 0 and bool(sess.finished.all()):
-                        new = torch.cat(parts, 1)
-                        hit = (new == eos).int().argmax(1)  # first eos per row (every row has one: all are finished)
-                        done = int(hit.max()) + 1
-                        break
-            new = torch.cat(parts, 1)[:, :done]
-        else:
-            position_ids = None
-            if attention_mask is not None:
-                position_ids = (attention_mask.long().cumsum(-1) - 1).masked_fill(attention_mask == 0, 1)
-            out = self(input_ids=prompt, images=images, attention_mask=attention_mask, position_ids=position_ids, use_cache=True,
-                       return_dict=True)
-            past, mask = out.past_key_values, attention_mask
-            out_buf = torch.zeros(n_new, B, dtype=torch.long, device=dev)
-            ftok = forced.t().contiguous() if forced is not None else None
-            fmk = fm.t().contiguous() if fm is not None else None
-            finished = torch.zeros(B, dtype=torch.bool, device=dev)
-            seed_t = torch.tensor([seed], dtype=torch.long, device=dev)
-            step_t = torch.zeros(1, dtype=torch.long, device=dev)
-            tok = torch.empty(B, dtype=torch.long, device=dev)
-            uni = torch.zeros(B, dtype=torch.float32, device=dev) if greedy else None
-            for i in range(n_new):
-                scores = out.logits[:, -1].float()
-                from . import ops
-                ops.sample_logits(scores, temperature, top_k, top_p, vocab_limit=V, seed=seed_t, step=step_t, out_tokens=out_buf,
-                                  force_tok=ftok, force_mask=fmk, eos=eos, pad=pad, finished=finished if eos >= 0 else None,
-                                  tok_out=tok, advance_step=True, uniforms=uni)
-                if crit and stop_after(out_buf[: i + 1].t(), scores):
-                    done = i + 1
-                    break
-                if eos >= 0 and bool(finished.all()):
-                    done = i + 1
-                    break
-                if i + 1 == n_new:
-                    break
-                pos = None
-                if mask is not None:
-                    mask = torch.cat([mask, mask.new_ones(B, 1)], dim=1)
-                    pos = (mask.long().sum(-1) - 1)[:, None]
-                out = self(input_ids=tok[:, None].clone(), past_key_values=past, attention_mask=mask, position_ids=pos, use_cache=True,
-                           return_dict=True)
-                past = out.past_key_values
-            new = out_buf[:done].t()
-        if tokens is not None:
-            tokens[:, s0:s0 + new.shape[1]] = new
-            return tokens, done
-        return torch.cat([input_ids, new], dim=1), done
+        from . import generation
+        return generation.sampled_decode(self, input_ids, max_new_tokens, float(temperature), int(top_k), float(top_p), vocab_limit,
+                                         images, attention_mask, pad_token_id, self._draw_seed(generator), fast, use_graph)
 
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, images=None, max_new_tokens=None, max_length=None, do_sample=False,
@@ -1491,12 +1318,13 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
         bool | BoolTensor, a tensor counting when `.all()`; scores = that step's fp32 logits) returns True.  `images` go to the
         prefill only.  `fast` (default: batch <= 8) runs the decode kernels with one graph replay per token (one per host check
         when stopping criteria are given, chunks of 16 with eos only); otherwise the model forward is re-entered per token.
-        `num_beams > 1` with `do_sample=False` is beam search (`_beam_decode`; `length_penalty`, `early_stopping` True / False /
+        `num_beams > 1` with `do_sample=False` is beam search (`generation.beam_decode`; `length_penalty`, `early_stopping` True / False /
         "never", `num_return_sequences <= num_beams`; temperature, top-k and top-p do not apply, as in 4.35.2); it returns
         [B * num_return_sequences, <= max_length].  Beam sampling, group / constrained beam search, repetition penalty and the other
         unimplemented generation arguments raise NotImplementedError naming the argument; unknown keywords raise TypeError."""
+        from . import generation
         num_beams = kwargs.pop("num_beams", 1)
-        beam_args = {k: kwargs.pop(k) for k in ("num_return_sequences", "length_penalty", "early_stopping") if k in kwargs}
+        beam_args ={k: kwargs.pop(k) for k in ("num_return_sequences", "length_penalty", "early_stopping") if k in kwargs}
         beam = num_beams is not None and int(num_beams) > 1
         if beam and do_sample:
             raise NotImplementedError(f"generate: `num_beams={num_beams!r}` with do_sample=True (beam sampling) is not supported")
@@ -1549,8 +1377,8 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
                 raise ValueError(f"generate: `early_stopping` must be True, False or 'never', got {early!r}")
             if max_new_tokens <= 0:
                 return input_ids.repeat_interleave(nrs, 0)
-            return self._beam_decode(input_ids, max_new_tokens, nb, nrs, length_penalty, early, images, attention_mask,
-                                     eos_token_id, int(pad_token_id), stopping_criteria, fast, use_graph)
+            return generation.beam_decode(self, input_ids, max_new_tokens, nb, nrs, length_penalty, early, images, attention_mask,
+                                          eos_token_id, int(pad_token_id), stopping_criteria, fast, use_graph)
         if max_new_tokens <= 0:
             return input_ids
         seed = self._draw_seed(generator)
@@ -1558,92 +1386,9 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
         if greedy:
             # greedy search over the whole vocabulary: top-k 1 keeps the arg-max ties, u = 0 draws the first of them (argmax's choice)
             temperature, top_k, top_p = 1.0, 1, 1.0
-        return self._sampled_decode(input_ids, max_new_tokens, float(temperature), int(top_k or 0), float(top_p), None, images,
-                                    attention_mask, None, seed, fast, use_graph, eos=eos_token_id, pad=int(pad_token_id),
-                                    stopping_criteria=stopping_criteria, greedy=greedy)[0]
-
-    @torch.no_grad()
-    def _beam_decode(self, input_ids, max_new_tokens, nb, nrs, length_penalty, early_stopping, images, attention_mask, eos, pad,
-                     stopping_criteria, fast, use_graph):
-        """Beam search (INTEGRATION.md "Beam search"): every step's candidate selection and bookkeeping is one `dllm_beam_step` launch.
-        Fast path (B * nb <= 8 unless `fast=False`): `decode.BeamDecodeSession`, one graph replay per token over a copy-free KV cache;
-        the host reads the done flags between chunks of 16 replays, or after every replay when stopping criteria are given.
-        Otherwise the model forward is re-entered per token with the cache reordered by `index_select`, as the reference does.
-        Criteria are called as crit(ids [B * nb, S + n] running beams, None)."""
-        from . import ops
-        B, S = input_ids.shape
-        dev = input_ids.device
-        R = B * nb
-        eos = -1 if eos is None else int(eos)
-        max_length = S + max_new_tokens
-        fast = (fast is None or bool(fast)) and R <= 8
-        crit = list(stopping_criteria or [])
-
-        def stop(ids):
-            for c in crit:
-                r = c(ids, None)
-                if bool(r.all()) if isinstance(r, torch.Tensor) else bool(r):
-                    return True
-            return False
-
-        running = input_ids.repeat_interleave(nb, 0)
-
-        def advance(state, i, running):
-            return torch.cat([running.index_select(0, state.parents[i].long()), state.tokens[i][:, None]], 1)
-
-        if fast:
-            from .decode import BeamDecodeSession
-            key = ("beam", B, nb, max_length + 1, use_graph, eos, pad, length_penalty, early_stopping, max_new_tokens)
-            sess = getattr(self, "_decode_session", None)
-            if sess is None or sess[0] != key:
-                sess = (key, BeamDecodeSession(self, B, nb, key[3], eos=eos, pad=pad, length_penalty=length_penalty,
-                                               early_stopping=early_stopping, max_new=max_new_tokens, use_graph=use_graph))
-                self._decode_session = sess
-            sess = sess[1]
-            sess.prefill(input_ids, images=images, attention_mask=attention_mask)
-            state, n = sess.beam, 1
-            if crit:
-                running = advance(state, 0, running)
-            halt = (bool(crit) and stop(running)) or bool(state.done.all())
-            while not halt and n < max_new_tokens:
-                m = 1 if crit else min(16, max_new_tokens - n)  # criteria see every step; the done flags are read between chunks
-                sess.generate(m)
-                if crit:
-                    running = advance(state, n, running)
-                n += m
-                halt = (bool(crit) and stop(running)) or bool(state.done.all())
-        else:
-            position_ids = None
-            if attention_mask is not None:
-                position_ids = (attention_mask.long().cumsum(-1) - 1).masked_fill(attention_mask == 0, 1)
-            out = self(input_ids=input_ids, images=images, attention_mask=attention_mask, position_ids=position_ids, use_cache=True,
-                       return_dict=True)
-            past = tuple((k.repeat_interleave(nb, 0), v.repeat_interleave(nb, 0)) for k, v in out.past_key_values)
-            mask = attention_mask.repeat_interleave(nb, 0) if attention_mask is not None else None
-            scores = out.logits[:, -1].float().repeat_interleave(nb, 0)
-            state = ops.BeamState(B, nb, max_new_tokens + 1, dev)
-            n = 0
-            for i in range(max_new_tokens):
-                ops.beam_step(scores, state, eos=eos, pad=pad, length_penalty=length_penalty, early_stopping=early_stopping,
-                              max_new=max_new_tokens)
-                n = i + 1
-                if crit:
-                    running = advance(state, i, running)
-                    if stop(running):
-                        break
-                if n == max_new_tokens or bool(state.done.all()):
-                    break
-                par = state.parents[i].long()
-                past = tuple((k.index_select(0, par), v.index_select(0, par)) for k, v in past)
-                pos = None
-                if mask is not None:
-                    mask = torch.cat([mask, mask.new_ones(R, 1)], dim=1)
-                    pos = (mask.long().sum(-1) - 1)[:, None]
-                out = self(input_ids=state.tok[:, None].clone(), past_key_values=past, attention_mask=mask, position_ids=pos,
-                           use_cache=True, return_dict=True)
-                past = out.past_key_values
-                scores = out.logits[:, -1].float()
-        return ops.beam_finalize(state, n, input_ids, nrs, max_length, eos, pad, length_penalty)
+        return generation.sampled_decode(self, input_ids, max_new_tokens, float(temperature), int(top_k or 0), float(top_p), None,
+                                         images, attention_mask, None, seed, fast, use_graph, eos=eos_token_id,
+                                         pad=int(pad_token_id), stopping_criteria=stopping_criteria, greedy=greedy)
 
     @torch.no_grad()
     def loglikelihood(self, requests, *, vocab_limit=None, max_batch_tokens=8192, max_batch_rows=64, return_token_logprobs=False):

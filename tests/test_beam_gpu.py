@@ -279,12 +279,13 @@ def test_fast_and_slow_generate_agree_when_decidable(tiny):
 
 
 def test_nb1_reproduces_greedy(tiny):
+    from dreamllm_amd import generation
     torch.manual_seed(2)
     B, S, N = 3, 17, 12
     ids = torch.randint(3, 30000, (B, S), device=DEV)
     ref = tiny.greedy_generate(ids, N, vocab_limit=None)
     for fast in (True, False):
-        out = tiny._beam_decode(ids, N, 1, 1, 1.0, False, None, None, None, 0, None, fast, True)
+        out = generation.beam_decode(tiny, ids, N, 1, 1, 1.0, False, None, None, None, 0, None, fast, True)
         assert torch.equal(out, ref), fast
 
 
