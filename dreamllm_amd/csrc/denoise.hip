@@ -11,6 +11,14 @@
 // Form: without rescale one thread per latent pixel, grid-stride.  With rescale one 512-thread block per image: two passes over
 // the image for the means and the centred sums of squares (fixed-order wave + block reductions, no atomics: two launches give the
 // same bits), then the update pass.  ~40-60 B per pixel: HBM / launch-latency bound.
+//
+// `dllm_cfg_dpm_step` is the same step for a second-order multistep scheduler (schedulers.py `multistep_coeffs`: DPM-Solver++),
+// whose update also needs the data prediction of the step before.  That history lives in an fp32 buffer hist [B][P][4] which
+// every launch overwrites with its own m0 and the next launch reads as m1:
+//   m0     = (x - s1a e) / sa  [epsilon]     m0 = sa x - s1a e  [v-prediction]        (e guided and rescaled as above)
+//   x_next = k_x x + k_m0 m0 + k_m1 m1 + sigma z      (m1: hist, read only when k_m1 != 0 -- on the first step it is uninitialised;
+//                                                       z: noise, read only when sigma != 0)
+// Same two forms; +16 B read and +16 B written per pixel.
 #include "common.h"
 
 namespace {
@@ -29,8 +37,20 @@ struct SchedArgs {
     float gs, phi, sa, s1a, k_x0, k_eps, k_x, sigma;
 };
 
+struct DpmArgs {
+    const bf16* pred;
+    float* lat;
+    float* hist;
+    const float* noise;
+    bf16* next_in;
+    int64_t B, P;
+    int G, vpred;
+    float gs, phi, sa, s1a, k_x, k_m0, k_m1, sigma;
+};
+
 // guided prediction of pixel i (flat b * P + p) and the conditional half's values (G = 1: both are pred)
-__device__ __forceinline__ void guided(const SchedArgs& a, int64_t i, f32x4& e, f32x4& ec) {
+template <typename Args>
+__device__ __forceinline__ void guided(const Args& a, int64_t i, f32x4& e, f32x4& ec) {
     if (a.G == 2) {
         const bf16x4 u = ld_bf16x4(a.pred + i * 4), c = ld_bf16x4(a.pred + (a.B * a.P + i) * 4);
 #pragma unroll
@@ -78,6 +98,35 @@ __global__ __launch_bounds__(SCHED_THREADS) void cfg_sched_kernel(SchedArgs a) {
     }
 }
 
+// multistep update of pixel i from its guided (and rescaled) prediction; hist: m1 in (only when it has a weight), m0 out
+__device__ __forceinline__ void update(const DpmArgs& a, int64_t i, f32x4 e) {
+    f32x4 x = *reinterpret_cast<f32x4*>(a.lat + i * 4);
+    f32x4 m1 = {0.f, 0.f, 0.f, 0.f}, z = {0.f, 0.f, 0.f, 0.f};
+    if (a.k_m1 != 0.f) m1 = *reinterpret_cast<const f32x4*>(a.hist + i * 4);
+    if (a.sigma != 0.f) z = *reinterpret_cast<const f32x4*>(a.noise + i * 4);
+    f32x4 m0;
+    bf16x8 o = zero_bf16x8();
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        m0[c] = a.vpred ? a.sa * x[c] - a.s1a * e[c] : (x[c] - a.s1a * e[c]) / a.sa;
+        x[c] = a.k_x * x[c] + a.k_m0 * m0[c] + a.k_m1 * m1[c] + a.sigma * z[c];
+        o[c] = (bf16)x[c];
+    }
+    *reinterpret_cast<f32x4*>(a.lat + i * 4) = x;
+    *reinterpret_cast<f32x4*>(a.hist + i * 4) = m0;
+    if (a.next_in != nullptr)
+        for (int g = 0; g < a.G; ++g) st_bf16x8(a.next_in + (g * a.B * a.P + i) * 8, o);
+}
+
+__global__ __launch_bounds__(SCHED_THREADS) void cfg_dpm_kernel(DpmArgs a) {
+    const int64_t n = a.B * a.P;
+    for (int64_t i = (int64_t)blockIdx.x * SCHED_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * SCHED_THREADS) {
+        f32x4 e, ec;
+        guided(a, i, e, ec);
+        update(a, i, e);
+    }
+}
+
 // block sum of two values in a fixed order (every thread receives the result)
 __device__ __forceinline__ f32x2 block_sum2(f32x2 v, f32x2* red) {
 #pragma unroll
@@ -95,6 +144,45 @@ __device__ __forceinline__ f32x2 block_sum2(f32x2 v, f32x2* red) {
 }
 
 __global__ __launch_bounds__(RESCALE_THREADS) void cfg_sched_rescale_kernel(SchedArgs a) {
+    __shared__ f32x2 red[RESCALE_WAVES];
+    const int64_t base = (int64_t)blockIdx.x * a.P;
+    const float cnt = (float)(a.P * 4);
+    // pass 1: means of the conditional prediction and of the guided one
+    f32x2 s = {0.f, 0.f};
+    for (int64_t p = threadIdx.x; p < a.P; p += RESCALE_THREADS) {
+        f32x4 e, ec;
+        guided(a, base + p, e, ec);
+        s[0] += (ec[0] + ec[1]) + (ec[2] + ec[3]);
+        s[1] += (e[0] + e[1]) + (e[2] + e[3]);
+    }
+    const f32x2 mean = block_sum2(s, red) / cnt;
+    // pass 2: centred sums of squares
+    f32x2 q = {0.f, 0.f};
+    for (int64_t p = threadIdx.x; p < a.P; p += RESCALE_THREADS) {
+        f32x4 e, ec;
+        guided(a, base + p, e, ec);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float dc = ec[k] - mean[0], de = e[k] - mean[1];
+            q[0] += dc * dc;
+            q[1] += de * de;
+        }
+    }
+    const f32x2 ss = block_sum2(q, red);
+    const float ratio = sqrtf(ss[0] / (cnt - 1.f)) / sqrtf(ss[1] / (cnt - 1.f));  // std(e_c) / std(e)
+    // pass 3: rescale + update
+    for (int64_t p = threadIdx.x; p < a.P; p += RESCALE_THREADS) {
+        f32x4 e, ec;
+        guided(a, base + p, e, ec);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) e[k] = a.phi * (e[k] * ratio) + (1.f - a.phi) * e[k];
+        update(a, base + p, e);
+    }
+}
+
+// the same three passes around the multistep update (a copy, not a shared template: factoring the passes out of the kernel above
+// changes its register allocation, and its generated code is meant to stay as it is)
+__global__ __launch_bounds__(RESCALE_THREADS) void cfg_dpm_rescale_kernel(DpmArgs a) {
     __shared__ f32x2 red[RESCALE_WAVES];
     const int64_t base = (int64_t)blockIdx.x * a.P;
     const float cnt = (float)(a.P * 4);
@@ -167,6 +255,45 @@ extern "C" int dllm_cfg_sched_step(const void* pred, float* latents, const float
         int64_t g = cdiv64(B * P, SCHED_THREADS);
         if (g > 8192) g = 8192;  // grid-stride the rest
         hipLaunchKernelGGL(cfg_sched_kernel, dim3((unsigned)g), dim3(SCHED_THREADS), 0, s, a);
+    }
+    return dllm_check_launch();
+}
+
+extern "C" int dllm_cfg_dpm_step(const void* pred, float* latents, float* hist, const float* noise, void* next_in, int64_t B, int64_t P,
+                                 int G, float guidance, float rescale, int v_prediction, float sqrt_at, float sqrt_1mat, float k_x,
+                                 float k_m0, float k_m1, float sigma, void* stream) {
+    if (B < 0 || P < 0 || B > 0x7FFFFFFFLL || (G != 1 && G != 2) || !(rescale >= 0.f) || (rescale > 0.f && P * 4 < 2))
+        return DLLM_ERR_SHAPE;
+    if (B == 0 || P == 0) return DLLM_OK;
+    if (pred == nullptr || latents == nullptr || hist == nullptr || (sigma != 0.f && noise == nullptr)) return DLLM_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(pred) & 7 || reinterpret_cast<uintptr_t>(latents) & 15 || reinterpret_cast<uintptr_t>(hist) & 15 ||
+        reinterpret_cast<uintptr_t>(noise) & 15 || reinterpret_cast<uintptr_t>(next_in) & 15)
+        return DLLM_ERR_ALIGN;
+    DpmArgs a;
+    a.pred = (const bf16*)pred;
+    a.lat = latents;
+    a.hist = hist;
+    a.noise = noise;
+    a.next_in = (bf16*)next_in;
+    a.B = B;
+    a.P = P;
+    a.G = G;
+    a.vpred = v_prediction ? 1 : 0;
+    a.gs = guidance;
+    a.phi = rescale;
+    a.sa = sqrt_at;
+    a.s1a = sqrt_1mat;
+    a.k_x = k_x;
+    a.k_m0 = k_m0;
+    a.k_m1 = k_m1;
+    a.sigma = sigma;
+    hipStream_t s = (hipStream_t)stream;
+    if (rescale > 0.f) {
+        hipLaunchKernelGGL(cfg_dpm_rescale_kernel, dim3((unsigned)B), dim3(RESCALE_THREADS), 0, s, a);
+    } else {
+        int64_t g = cdiv64(B * P, SCHED_THREADS);
+        if (g > 8192) g = 8192;  // grid-stride the rest
+        hipLaunchKernelGGL(cfg_dpm_kernel, dim3((unsigned)g), dim3(SCHED_THREADS), 0, s, a);
     }
     return dllm_check_launch();
 }

@@ -31,14 +31,18 @@ def graph_denoise_mode(use_graph, sched, guidance_scale, guidance_rescale, eta, 
       "ddim"  -- deterministic DDIM + CFG, no rescale, no callback: hipGraph replay + `dllm_cfg_ddim_step` (the original fast path);
       "sched" -- any scheduler with `step_coeffs` (DDPM, DDIM with eta), with or without CFG / rescale / callback: hipGraph replay +
                  `dllm_cfg_sched_step`;
-      None    -- the plain per-step loop (`use_graph=False`, a scheduler without `step_coeffs`, num_images_per_prompt != 1,
-                 an inpainting-style UNet)."""
+      "multistep" -- a scheduler with `multistep_coeffs` (DPM-Solver++), same freedom: hipGraph replay + `dllm_cfg_dpm_step`, the
+                 previous step's data prediction kept in a device buffer;
+      None    -- the plain per-step loop (`use_graph=False`, a scheduler with neither `step_coeffs` nor `multistep_coeffs`,
+                 num_images_per_prompt != 1, an inpainting-style UNet)."""
     if not (use_graph and num_images_per_prompt == 1 and in_channels == 4):
         return None
     if (guidance_scale > 1.0 and guidance_rescale == 0.0 and eta == 0.0 and hasattr(sched, "step_cfg_fused_")
             and callback is None):
         return "ddim"
-    return "sched" if hasattr(sched, "step_coeffs") else None
+    if hasattr(sched, "step_coeffs"):
+        return "sched"
+    return "multistep" if hasattr(sched, "multistep_coeffs") else None
 
 
 def predraw_step_noise(shape, coeffs, generator, device):
@@ -520,7 +524,9 @@ class StableDiffusionHead(MultimodalHead):
         the cross-attention K/V of the conditioning tokens) is cached per shape and CFG factor G.
         mode "ddim" (see `graph_denoise_mode`): deterministic DDIM + CFG through `dllm_cfg_ddim_step`.  mode "sched": any
         scheduler with `step_coeffs`, CFG (G = 2) or not (G = 1, the UNet captured at batch B), guidance rescale, ancestral noise
-        drawn ahead of the loop in the plain loop's order (`predraw_step_noise`), `callback(i, t, latents)` as the plain loop."""
+        drawn ahead of the loop in the plain loop's order (`predraw_step_noise`), `callback(i, t, latents)` as the plain loop.
+        mode "multistep": the same for a scheduler with `multistep_coeffs`, through `dllm_cfg_dpm_step`; the history buffer (the
+        previous step's data prediction) is allocated here, per call.  The captured graph is the same one for every mode."""
         B, C, H, W = latents.shape
         do_cfg = guidance_scale > 1.0
         G = 2 if (mode == "ddim" or do_cfg) else 1
@@ -587,7 +593,11 @@ class StableDiffusionHead(MultimodalHead):
             raise ValueError(sched.config.prediction_type)
         vpred = sched.config.prediction_type == "v_prediction"
         ts_list = list(timesteps.tolist() if torch.is_tensor(timesteps) else timesteps)
-        coeffs = [sched.step_coeffs(t, eta) for t in ts_list]
+        if mode == "multistep":
+            coeffs = [sched.multistep_coeffs(i) for i in range(len(ts_list))]
+            hist = torch.empty_like(lat)  # first read on the first second-order step, after the step before has written it
+        else:
+            coeffs = [sched.step_coeffs(t, eta) for t in ts_list]
         noise = predraw_step_noise(latents.shape, coeffs, generator, dev)
         phi = guidance_rescale if do_cfg else 0.0  # the reference rescales only with CFG (:829)
         k = 0
@@ -598,7 +608,10 @@ class StableDiffusionHead(MultimodalHead):
             if c.draws:
                 z = noise[k]
                 k += 1
-            ops.cfg_sched_step_(ent["pred"], lat, z, x_in, guidance_scale, phi, c, vpred)
+            if mode == "multistep":
+                ops.cfg_dpm_step_(ent["pred"], lat, hist, z, x_in, guidance_scale, phi, c, vpred)
+            else:
+                ops.cfg_sched_step_(ent["pred"], lat, z, x_in, guidance_scale, phi, c, vpred)
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, lat.permute(0, 3, 1, 2).contiguous())
         return lat.permute(0, 3, 1, 2).contiguous()

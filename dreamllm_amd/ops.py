@@ -1658,6 +1658,30 @@ def cfg_sched_step_(pred, latents, noise, next_in, guidance, rescale, coeffs, v_
     return latents
 
 
+def cfg_dpm_step_(pred, latents, hist, noise, next_in, guidance, rescale, coeffs, v_prediction=False):
+    """Fused CFG combine (+ guidance rescale) + multistep scheduler step from `coeffs` (schedulers.MultistepCoeffs) + next UNet
+    input, in place on the fp32 NHWC latents [B,H,W,4].  hist fp32 like latents: the data prediction of the step before (read only
+    when coeffs.k_m1 != 0), overwritten with this step's.  pred, noise and next_in as in `cfg_sched_step_`."""
+    _need_gpu(pred, latents, hist, noise, next_in)
+    B, P = latents.shape[0], latents.numel() // (4 * max(latents.shape[0], 1))
+    if pred.dtype != torch.bfloat16 or latents.dtype != torch.float32 or latents.shape[-1] != 4 or not latents.is_contiguous():
+        raise ValueError("cfg_dpm_step_: pred bf16 [G*B,...,4], latents fp32 contiguous [B,...,4]")
+    G = pred.numel() // max(latents.numel(), 1)
+    if pred.numel() != G * latents.numel() or not pred.is_contiguous():
+        raise ValueError(f"cfg_dpm_step_: pred {tuple(pred.shape)} is not G x latents {tuple(latents.shape)}")
+    if hist is None or hist.dtype != torch.float32 or hist.shape != latents.shape or not hist.is_contiguous():
+        raise ValueError("cfg_dpm_step_: hist must be fp32 contiguous like latents")
+    if noise is not None and (noise.dtype != torch.float32 or noise.shape != latents.shape or not noise.is_contiguous()):
+        raise ValueError("cfg_dpm_step_: noise must be fp32 contiguous like latents")
+    if next_in is not None and (next_in.dtype != torch.bfloat16 or next_in.numel() != 2 * G * latents.numel()
+                                or not next_in.is_contiguous()):
+        raise ValueError("cfg_dpm_step_: next_in must be bf16 contiguous [G*B,...,8]")
+    c = coeffs
+    check("dllm_cfg_dpm_step", _p(pred), _p(latents), _p(hist), _p(noise), _p(next_in), B, P, G, float(guidance), float(rescale),
+          int(v_prediction), c.sqrt_at, c.sqrt_1mat, c.k_x, c.k_m0, c.k_m1, c.sigma, _stream())
+    return latents
+
+
 class PackedAttnFn(torch.autograd.Function):
     """Self-attention on a packed [B,S,3,H,D] QKV GEMM output; the backward writes dQ/dK/dV straight into one packed
     buffer (no zero-filled slice gradients)."""

@@ -265,6 +265,14 @@ int dllm_cfg_ddim_step(const void* pred, float* latents, void* next_in, int64_t 
 int dllm_cfg_sched_step(const void* pred, float* latents, const float* noise, void* next_in, int64_t B, int64_t P, int G,
                         float guidance, float rescale, int v_prediction, float sqrt_at, float sqrt_1mat, float k_x0, float k_eps,
                         float k_x, float sigma, void* stream);
+/* The same step for a multistep scheduler (schedulers.py `multistep_coeffs`: DPM-Solver++ at order 1 and 2), whose update also takes
+ * the data prediction of the step before: hist fp32 [B,P,4], never NULL, always overwritten with this step's m0 and read (as m1) only
+ * when k_m1 != 0, so the first step may be given an uninitialised buffer.  pred / latents / noise / next_in and the guidance
+ * arithmetic as above; m0 = (x - sqrt_1mat e) / sqrt_at (epsilon) or sqrt_at x - sqrt_1mat e (v_prediction);
+ * x_next = k_x x + k_m0 m0 + k_m1 m1 + sigma noise.  Deterministic: no atomics. */
+int dllm_cfg_dpm_step(const void* pred, float* latents, float* hist, const float* noise, void* next_in, int64_t B, int64_t P, int G,
+                      float guidance, float rescale, int v_prediction, float sqrt_at, float sqrt_1mat, float k_x, float k_m0,
+                      float k_m1, float sigma, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------- greedy decode
  * Token step of the KV-cache decode loop (omni/eval/language_eval/modeling_dreamllm.py:76-97): every nn.Linear of

@@ -2,6 +2,7 @@
 
     python tools/denoise_bench.py                 # every leg
     python tools/denoise_bench.py --legs A,B,E    # a subset
+    python tools/denoise_bench.py --runs ddpm:50,dpm:50,ddim:50,dpm:25,dpm:20 --batch 1,8    # chosen scheduler:steps pairs
 
 Legs (one MI355X, real SD-2.1 / SDXL dimensions, random-init weights, prompt embeddings of 64 / 196 dream queries):
   A  control: DDIM eta 0, CFG 7.5, 50 steps, B_img 1 and 8  (the original graphed path, `dllm_cfg_ddim_step`)
@@ -9,6 +10,9 @@ Legs (one MI355X, real SD-2.1 / SDXL dimensions, random-init weights, prompt emb
   C  the COCO eval recipe: DDPM, CFG 2.0, 150 steps, B 24 at 512 px (also images/s)
   D  SDXL (projects/dreamllm_sdxl/inf.py): DDPM, guidance_scale 0.0 (no CFG), 100 steps, 1024 px, B_img 1
   E  DDIM, CFG 7.5 + guidance_rescale 0.7, 50 steps, B_img 1
+--runs replaces the legs by leg "R": SD-2.1 at 512 px, CFG 7.5 (--guidance), a seeded generator, one configuration per
+scheduler:steps pair and batch size; schedulers: ddpm, ddim, dpm (DPM-Solver++ 2M, graph mode "multistep"), dpm-sde.  It times a
+sampler at the step count it is run at beside another (DPM at 20 or 25 steps beside DDIM at 50): step counts, not image quality.
 Per configuration: one warm-up call of each loop (graph capture), then graph and plain loop alternate, median of --reps whole
 loops each.  Prints one JSON line per configuration: steps/s and ms/step of both loops, and the rel-L2 between their final
 latents on the same seed.
@@ -56,6 +60,24 @@ def _configs():
     return c
 
 
+def _scheduler(name):
+    from dreamllm_amd.schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
+    if name == "dpm-sde":
+        def DPMSolverSDE():
+            return DPMSolverMultistepScheduler(algorithm_type="sde-dpmsolver++")
+        return DPMSolverSDE
+    return dict(ddpm=DDPMScheduler, ddim=DDIMScheduler, dpm=DPMSolverMultistepScheduler)[name]
+
+
+def _run_configs(runs, batches, guidance):
+    c = []
+    for pair in runs.split(","):
+        name, steps = pair.split(":")
+        for b in batches:
+            c.append(dict(leg="R", head="sd21", sched=_scheduler(name), gs=guidance, phi=0.0, steps=int(steps), B=b, px=512, gen="seed"))
+    return c
+
+
 def _run(head, cfg, use_graph, steps=None):
     nq = 196 if cfg["head"] == "sdxl" else 64
     g = torch.Generator().manual_seed(42)
@@ -79,9 +101,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default="A,B,C,D,E")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--runs", default=None, help="scheduler:steps pairs (ddpm, ddim, dpm, dpm-sde), e.g. dpm:20,ddim:50; replaces --legs")
+    ap.add_argument("--batch", default="1", help="batch sizes of --runs, e.g. 1,8")
+    ap.add_argument("--guidance", type=float, default=7.5, help="guidance scale of --runs")
     a = ap.parse_args()
     legs = set(a.legs.split(","))
-    cfgs = [c for c in _configs() if c["leg"] in legs]
+    if a.runs:
+        cfgs = _run_configs(a.runs, [int(b) for b in a.batch.split(",")], a.guidance)
+    else:
+        cfgs = [c for c in _configs() if c["leg"] in legs]
     heads = _heads(any(c["head"] == "sd21" for c in cfgs), any(c["head"] == "sdxl" for c in cfgs))
     from dreamllm_amd.modeling_plugins import graph_denoise_mode
     for cfg in cfgs:
