@@ -50,6 +50,8 @@ SIGNATURES = {
                       [c_int] * 3 + [c_void_p] * 2 + [c_i64] + [c_void_p] * 4,
     "dllm_sample_logits": [c_void_p, c_i64, c_int, c_int, c_float, c_int, c_float] + [c_void_p] * 3 + [c_int] + [c_void_p] * 3 +
                           [c_i64] * 3 + [c_void_p] * 7,
+    "dllm_interleave_park": [c_void_p, c_int, c_i64, c_i64, c_int] + [c_void_p] * 7,
+    "dllm_image_to_clip": [c_void_p, c_void_p] + [c_int] * 7 + [c_float] * 6 + [c_void_p],
     "dllm_score_rows": [c_void_p, c_i64, c_i64, c_int] + [c_void_p] * 7 + [c_int] + [c_void_p] * 3,
     "dllm_score_segments": [c_void_p] * 3 + [c_i64, c_i64] + [c_void_p] * 3,
     "dllm_gemv_attn_combine": [c_void_p] * 4 + [c_int] * 4 + [c_i64] * 4 + [c_int, c_void_p],

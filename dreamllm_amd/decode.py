@@ -24,7 +24,7 @@ import math
 import torch
 
 from . import ops
-from .generation import check_left_padded, left_pad_position_ids
+from .generation import check_left_padded, left_pad_position_ids, phase_seed
 
 
 class GreedyDecodeSession:
@@ -107,10 +107,14 @@ class GreedyDecodeSession:
             hf, _, _ = ops.rmsnorm_fwd(x, m.model.norm.weight, eps)
             logits = ops.gemv(hf, m.lm_head.weight, out_dtype=torch.float32)
         self._choose(logits)
+        self._advance()
+        return logits
+
+    def _advance(self):
+        """End of a token step (inside the captured graph): every row moves on to its next position and cache slot."""
         self.pos.add_(1)
         self.kv_len.add_(1)
         self.slot.add_(1)
-        return logits
 
     def _choose(self, logits):
         """Token choice of a step (inside the captured graph): writes `tok` and `out_tokens[step]`, advances the step."""
@@ -332,3 +336,97 @@ class BeamDecodeSession(GreedyDecodeSession):
         ops.beam_step(self.first_logits, self.beam, eos=self.eos, pad=self.pad, length_penalty=self.length_penalty,
                       early_stopping=self.early_stopping, max_new=self.max_new)
         return self.tok.clone()
+
+
+class InterleavedDecodeSession(SampledDecodeSession):
+    """`SampledDecodeSession` for interleaved text-and-image generation (`generation.interleaved_decode`, INTEGRATION.md "Interleaved
+    generation"): rows stop on their own inside a chunk of graph replays, and the host appends whole blocks of embeddings to a row.
+
+    * The end of the token step is `ops.interleave_park` (csrc/interleave.hip) in place of the three unconditional increments: a row
+      that has just emitted eos or `trigger` (<dream_start>) is parked (`parked` int32 [B]: 0 running, 1 eos, 2 trigger; `park_step`
+      = the number of tokens of the phase up to and including that one) and stops advancing; it keeps re-running its step on one
+      dead cache slot, and the host ignores what it emits.
+    * `bias` fp32 [B, V] is added to the logits before the token choice (zero, or -inf at the trigger id for a row whose image budget
+      or space is used up); the captured graph reads its current values.
+    * A PHASE is the stretch between two points at which every row is parked.  Its first token is chosen from given logits
+      (`prefill`: the prompt's; `begin_phase`: the logits at <im_end> of the rows that resume), its draws are keyed by
+      `generation.phase_seed(seed, phase)` at counter (row, token index within the phase).  A row alive in phase p has produced
+      exactly p images, so a row's draws depend on its row index and its own history, not on the other rows of the batch.
+    * `append_block(b, embeds)`: one forward of a block of embeddings on the MFMA path against the row's past K/V, taken as views of
+      the session cache, with the new K/V written back at the row's own slots."""
+
+    def __init__(self, model, batch_size: int, max_len: int, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                 eos: int | None = None, pad: int = 0, trigger: int = -1, fixed_u: float | None = None, **kw):
+        super().__init__(model, batch_size, max_len, temperature, top_k, top_p, eos=eos, pad=pad, fixed_u=fixed_u, vocab_limit=None, **kw)
+        dev = self.tok.device
+        self.trigger = int(trigger)
+        self.parked = torch.zeros(batch_size, dtype=torch.int32, device=dev)
+        self.park_step = torch.zeros(batch_size, dtype=torch.long, device=dev)
+        self.bias = torch.zeros(batch_size, model.config.vocab_size, dtype=torch.float32, device=dev)
+        self.base_seed = 0
+
+    def _choose(self, logits):
+        logits.add_(self.bias)
+        self._sample(logits)
+
+    def _advance(self):
+        ops.interleave_park(self.tok, self.parked, self.park_step, self.rng_step, eos=self.eos, trigger=self.trigger,
+                            pos=self.pos.view(-1), kv_len=self.kv_len, slot=self.slot)
+
+    def _state(self):
+        return super()._state() + (self.parked, self.park_step)
+
+    def _choose_first(self, logits, forced_tok, forced_mask):
+        self.parked.zero_()
+        self.park_step.zero_()
+        return self.begin_phase(logits.float(), 0)
+
+    @torch.no_grad()
+    def prefill(self, input_ids, images=None, attention_mask=None, seed: int = 0):
+        """Prompt through the model, cache filled, phase 0 begun: returns its first token [B] (a row may be parked by it already)."""
+        self.base_seed = int(seed)
+        return super().prefill(input_ids, images=images, attention_mask=attention_mask, seed=seed)
+
+    @torch.no_grad()
+    def begin_phase(self, logits, phase: int):
+        """First token of phase `phase` from `logits` fp32 [B, V] (rows that stay parked: any finite values, their token is ignored):
+        restarts the step counter, keys the phase's draws, chooses and parks without advancing -- the rows' state already describes
+        the slot and position of this token."""
+        self.seed.fill_(phase_seed(self.base_seed, phase))
+        self._fmask_all[0].zero_()
+        self.rng_step.zero_()
+        self.status.zero_()
+        self.finished.copy_(self.parked != 0)
+        self.generated = 0
+        self.first_logits = logits + self.bias
+        self._sample(self.first_logits)
+        ops.interleave_park(self.tok, self.parked, self.park_step, self.rng_step, eos=self.eos, trigger=self.trigger)
+        return self._out_all[0].clone()
+
+    def set_ban(self, b: int, banned: bool):
+        """Remove (or allow again) the trigger id from row b's token choice."""
+        if self.trigger >= 0:
+            self.bias[b, self.trigger] = float("-inf") if banned else 0.0
+
+    def set_row(self, b: int, cur: int, pos: int, parked: int = 0):
+        """Host-side reset of row b: its next token goes to cache slot `cur` of the row with position id `pos`."""
+        self.pos[b, 0] = pos
+        self.kv_len[b] = cur + 1
+        self.slot[b] = b * self.max_len + cur
+        self.parked[b] = parked
+
+    @torch.no_grad()
+    def append_block(self, b: int, embeds, start: int, cur: int, pos: int):
+        """Run `embeds` [1, L, d] as the next L positions of row b: its valid cache is slots [start, cur), the block takes position
+        ids pos .. pos + L - 1 and its K/V go to slots [cur, cur + L).  -> the block's last hidden states [1, L, d]."""
+        L = embeds.shape[1]
+        if cur + L > self.max_len:
+            raise ValueError("append_block: the block does not fit the KV cache")
+        past = tuple((k[b:b + 1, start:cur].transpose(1, 2), v[b:b + 1, start:cur].transpose(1, 2)) for k, v in zip(self.kc, self.vc))
+        position_ids = torch.arange(pos, pos + L, dtype=torch.long, device=embeds.device)[None]
+        out = self.model.model._forward(inputs_embeds=embeds, position_ids=position_ids, past_key_values=past, use_cache=True,
+                                        return_dict=True)
+        for li, (k, v) in enumerate(out.past_key_values):  # reference layout [1, Hkv, past + L, D]
+            self.kc[li][b, cur:cur + L].copy_(k[0, :, -L:].transpose(0, 1))
+            self.vc[li][b, cur:cur + L].copy_(v[0, :, -L:].transpose(0, 1))
+        return out.last_hidden_state

@@ -1,13 +1,16 @@
 """Host side of text generation for `DreamLLMForCausalMLM`: the protocols of the reference's generation loops, each written once.
 
-`greedy_generate`, `sample_generate` and `generate` on the model are argument handling plus one call of a driver here
-(`greedy_decode`, `sampled_decode`, `beam_decode`).  A driver either runs a `decode` session (fast path: one hipGraph replay per
+`greedy_generate`, `sample_generate`, `generate` and `generate_interleaved` on the model are argument handling plus one call of a
+driver here (`greedy_decode`, `sampled_decode`, `beam_decode`, `interleaved_decode`).  A driver either runs a `decode` session (fast path: one hipGraph replay per
 token, the host only reads flags between chunks of replays -- `run_chunked`) or re-enters the model forward per token like the
 reference (`ModelStepper`).  The drivers differ in how a token is chosen (arg-max / `ops.sample_logits` / `ops.beam_step`);
 position ids, the ragged-prompt protocol, the stopping-criterion rule and the session cache are shared.  Everything above the
 drivers is index arithmetic on whatever device its arguments live on, so it runs (and is tested) without a GPU.
 """
 from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import NamedTuple
 
 import torch
 
@@ -283,3 +286,280 @@ def beam_decode(model, input_ids, max_new_tokens, nb, nrs, length_penalty, early
                 break
             stepper.step(state.tok.clone(), parents=state.parents[i].long())  # a copy: the kernel overwrites `tok` in the next step
     return ops.beam_finalize(state, n, input_ids, nrs, max_length, eos, pad, length_penalty)
+
+
+# ---------------------------------------------------------------------------------------------- interleaved text and images
+@dataclass
+class InterleavedOutput:
+    """Result of `DreamLLMForCausalMLM.generate_interleaved`: `sequences[b]` 1-D LongTensor (row b's prompt without its padding, then
+    everything generated, layout ids in place); `images[b]` the row's images, fp32 [3, H, W] in [0, 1], in document order;
+    `image_positions[b]` the index of each <dream_start> in `sequences[b]`."""
+    sequences: list
+    images: list
+    image_positions: list
+
+
+class InterleaveLayout(NamedTuple):
+    """Ids and lengths of an image in a document, as the reference's data builder lays it out (omni/data/builders/
+    builder_dreamllm.py:110-128): <dream_start> [n_query placeholder ids] <dream_end> <im_start> [n_patch <im_patch> ids] <im_end>."""
+    trigger: int
+    placeholder: int
+    dream_end: int
+    im_start: int
+    im_patch: int
+    im_end: int
+    n_query: int
+    n_patch: int
+
+    @property
+    def block_len(self):
+        """Layout tokens that follow an emitted <dream_start>."""
+        return self.n_query + 1 + 1 + self.n_patch + 1
+
+    def ids_after_trigger(self):
+        return [self.placeholder] * self.n_query + [self.dream_end, self.im_start] + [self.im_patch] * self.n_patch + [self.im_end]
+
+
+def assemble_row(prompt, segments, layout):
+    """One row's document: `prompt` (1-D LongTensor) followed, per segment (tokens, image), by the chosen `tokens` (1-D; with `image`
+    the last of them is the <dream_start> the row emitted) and, with `image`, the layout ids the runtime supplied.
+    -> (sequence 1-D LongTensor, [index of each <dream_start>])."""
+    parts, positions, n = [prompt], [], int(prompt.numel())
+    for tokens, image in segments:
+        tokens = torch.as_tensor(tokens, dtype=torch.long, device=prompt.device).reshape(-1)
+        parts.append(tokens)
+        n += int(tokens.numel())
+        if image:
+            if tokens.numel() == 0 or int(tokens[-1]) != layout.trigger:
+                raise ValueError("assemble_row: an image segment must end with the trigger id")
+            positions.append(n - 1)
+            parts.append(torch.tensor(layout.ids_after_trigger(), dtype=torch.long, device=prompt.device))
+            n += layout.block_len
+    return torch.cat(parts), positions
+
+
+def assemble_interleaved(prompts, phases, layout):
+    """Row sequences of a batch from what the decode session recorded.  `prompts`: B 1-D LongTensors; `phases`: one (tokens, taken,
+    image) per phase -- `tokens` LongTensor [n, B] are the per-step tokens of the phase (the first from the phase's opening logits,
+    then one per graph replay), `taken[b]` is the row's park step (how many of them belong to row b: up to and including the token
+    it parked on; 0 for a row that was not alive), `image[b]` says that the row parked on <dream_start> and got its image block.
+    -> (sequences, image_positions)."""
+    seqs, poss = [], []
+    for b, prompt in enumerate(prompts):
+        segs = [(tokens[: int(taken[b]), b], bool(image[b])) for tokens, taken, image in phases if int(taken[b]) > 0]
+        seq, pos = assemble_row(prompt, segs, layout)
+        seqs.append(seq)
+        poss.append(pos)
+    return seqs, poss
+
+
+def interleave_layout(model):
+    sp = model.config.special_tokens2ids_dict["additional_special_tokens"]
+    return InterleaveLayout(trigger=sp["<dream_start>"], placeholder=sp[model._dream_patch_token], dream_end=sp["<dream_end>"],
+                            im_start=sp["<im_start>"], im_patch=sp["<im_patch>"], im_end=sp["<im_end>"],
+                            n_query=model.model.dream_embedding.embed_len, n_patch=model.model.clip_vision_embedding.embed_len)
+
+
+def trigger_room(layout, prompt_len, max_new_tokens, max_positions):
+    """Largest index c (0-based, among the new tokens) at which a row may still emit <dream_start>: the trigger and the two blocks
+    must fit `max_new_tokens` (c + 1 + block_len <= max_new_tokens) and the position ids (<im_end> sits at position prompt_len + c +
+    block_len < max_positions).  Negative: never."""
+    return min(max_new_tokens - 1 - layout.block_len, max_positions - 1 - layout.block_len - prompt_len)
+
+
+def clip_pixels(model, image):
+    """Decoded image fp32 [1, 3, H, W] in [0, 1] -> CLIP pixel values on the device (`ops.image_to_clip`), sized and normalised by
+    the CLIP embedding's processor config.  The kernel resizes the shorter side to the size it then crops to, as OpenAI CLIP's
+    processor does (`size["shortest_edge"] == crop_size`); a processor whose two sizes differ raises."""
+    proc = model.model.clip_vision_embedding.processor
+    crop = proc.crop_size
+    crop = (crop["height"], crop["width"]) if isinstance(crop, dict) else (int(crop), int(crop))
+    edge = getattr(proc, "size", None)
+    edge = edge.get("shortest_edge", crop[0]) if isinstance(edge, dict) else (crop[0] if edge is None else int(edge))
+    if crop[0] != crop[1] or edge != crop[0]:
+        raise ValueError(f"clip_pixels: the CLIP processor resizes to {edge} and crops to {crop}; the hand-off needs one square size")
+    return ops.image_to_clip(image, crop[0], proc.image_mean, proc.image_std, out_dtype=model.dtype)
+
+
+_MIX = 0x9E3779B97F4A7C15  # odd 64-bit constant (2^64 / golden ratio): spreads small indices over the whole key space
+
+
+def _i64(x):
+    return (x + 2 ** 63) % 2 ** 64 - 2 ** 63
+
+
+def phase_seed(seed, phase):
+    """Philox key of the token draws of phase `phase` (int64): seed + phase * _MIX, wrapped."""
+    return _i64(int(seed) + int(phase) * _MIX)
+
+
+def image_generator(seed, row, index):
+    """CPU generator of the `index`-th image of row `row` (latents and ancestral noise of its denoising loop), derived from the
+    call's seed: an image's noise depends on (seed, row, index) alone -- not on the order in which a path synthesises the images
+    of a batch, and not on the other rows."""
+    return torch.Generator().manual_seed(_i64(int(seed) ^ ((1 + int(row) + 64 * (1 + int(index))) * _MIX)) & (2 ** 63 - 1))
+
+
+def _image_event(model, layout, append, synthesize):
+    """A row has emitted <dream_start>: `append(embeds [1, L, d]) -> last hidden states [1, L, d]` runs a block as the row's next L
+    positions.  [<dream_start>, queries, <dream_end>] -> the queries' hidden states -> `synthesize` -> the image -> CLIP pixel values
+    -> [<im_start>, patch embeddings, <im_end>].  -> (image fp32 [3, H, W], fp32 logits [V] at <im_end>)."""
+    dq = model.model.prepare_dream_queries_with_special_token(1).to(model.dtype)
+    hidden = append(dq)
+    image = synthesize(hidden[:, 1:-1, :])
+    feats = model.model.clip_vision_embedding(clip_pixels(model, image))
+    sp = model.model.embed(torch.as_tensor([[layout.im_start, layout.im_end]], device=dq.device))
+    hidden = append(torch.cat([sp[:, :1], feats.to(sp.dtype), sp[:, 1:]], 1))
+    logits = ops.linear(hidden[:, -1:], model.lm_head.weight, out_fp32=True)
+    return image[0], logits[0, 0].float()
+
+
+@torch.no_grad()
+def interleaved_decode(model, input_ids, max_new_tokens, max_images, temperature, top_k, top_p, images, attention_mask, seed, fast,
+                       use_graph, eos, pad, greedy, synthesize):
+    """Body of `DreamLLMForCausalMLM.generate_interleaved` (INTEGRATION.md "Interleaved generation").  Token choice as `sampled_decode`
+    (`ops.sample_logits` over the whole vocabulary); a row that emits <dream_start> gets [<dream_start>, queries, <dream_end>] and,
+    after `synthesize(prompt_embeds [1, n_query, d], row) -> image fp32 [1, 3, H, W] in [0, 1]`, [<im_start>, CLIP patch embeddings,
+    <im_end>] appended to its cache and carries on from the logits at <im_end>.
+
+    `fast=False` (and B > 8) is the specification: every row on its own, the model forward re-entered per token and per block with
+    `past_key_values`.  The fast path runs `decode.InterleavedDecodeSession`: chunks of up to 16 graph replays, `parked` read between
+    chunks; when no row is running, the rows parked on the trigger get their blocks (`append_block`) and the next phase begins."""
+    B, S = input_ids.shape
+    dev = input_ids.device
+    layout = interleave_layout(model)
+    V = model.config.vocab_size
+    eos = -1 if eos is None else int(eos)
+    if fast is None:
+        fast = B <= 8
+    if attention_mask is not None:
+        plen = [int(n) for n in (attention_mask != 0).sum(-1).tolist()]
+    else:
+        plen = [S] * B
+    prompts = [input_ids[b, S - plen[b]:] for b in range(B)]
+    cmax = [trigger_room(layout, plen[b], max_new_tokens, model.config.max_position_embeddings) for b in range(B)]
+    out_images = [[] for _ in range(B)]
+
+    if not fast:
+        im_rows = (input_ids == layout.im_start).sum(-1).tolist() if images is not None else [0] * B
+        seqs, poss = [], []
+        buf = torch.zeros(B, V, dtype=torch.float32, device=dev)
+        uni = torch.zeros(B, dtype=torch.float32, device=dev) if greedy else None
+        tok = torch.empty(B, dtype=torch.long, device=dev)
+        for b in range(B):
+            i0 = int(sum(im_rows[:b]))
+            stepper = ModelStepper(model, prompts[b][None], images[i0:i0 + int(im_rows[b])] if im_rows[b] else None, None)
+
+            def append(embeds):
+                out = model.model._forward(inputs_embeds=embeds, past_key_values=stepper.past, use_cache=True, return_dict=True)
+                stepper.past = out.past_key_values
+                return out.last_hidden_state
+
+            logits = stepper.logits[0].float()
+            segs, cur, cnt, n_img, phase, step = [], [], 0, 0, 0, 0
+            while cnt < max_new_tokens:
+                buf[b].copy_(logits)
+                if n_img >= max_images or cnt > cmax[b]:
+                    buf[b, layout.trigger] = float("-inf")
+                ops.sample_logits(buf, temperature, top_k, top_p, vocab_limit=V, seed=phase_seed(seed, phase),
+                                  step=step, tok_out=tok, uniforms=uni)
+                t = int(tok[b])
+                step += 1
+                cnt += 1
+                cur.append(t)
+                if t == eos:
+                    break
+                if t == layout.trigger:
+                    image, logits = _image_event(model, layout, append, lambda e: synthesize(e, b, n_img))
+                    out_images[b].append(image)
+                    segs.append((cur, True))
+                    cur, cnt, n_img, phase, step = [], cnt + layout.block_len, n_img + 1, phase + 1, 0
+                elif cnt < max_new_tokens:
+                    logits = stepper.step(tok[b:b + 1].clone())[0].float()
+            if cur:
+                segs.append((cur, False))
+            seq, pos = assemble_row(prompts[b], segs, layout)
+            seqs.append(seq)
+            poss.append(pos)
+        return InterleavedOutput(seqs, out_images, poss)
+
+    from .decode import InterleavedDecodeSession
+    max_len = S + max_new_tokens + 1
+    sess = cached_session(
+        model, ("interleave", B, max_len, use_graph, temperature, top_k, top_p, eos, int(pad), greedy, layout.trigger),
+        lambda: InterleavedDecodeSession(model, B, max_len, temperature, top_k, top_p, eos=eos, pad=pad, trigger=layout.trigger,
+                                         use_graph=use_graph, fixed_u=0.0 if greedy else None))
+    cnt, n_img = [0] * B, [0] * B                # new tokens so far (layout included), images so far
+    cur, pos = [S] * B, list(plen)               # cache slot and position id of the row's first token of the phase
+    start = [S - n for n in plen]
+    alive = list(range(B))
+    banned = [None] * B
+
+    def ban(b, c_next):
+        want = n_img[b] >= max_images or c_next > cmax[b]
+        if banned[b] != want:
+            sess.set_ban(b, want)
+            banned[b] = want
+
+    for b in range(B):
+        ban(b, 0)
+    sess.prefill(input_ids, images=images, attention_mask=attention_mask, seed=seed)
+    phases, phase = [], 0
+    while True:
+        parts, n_phase = [sess._out_all[:1].clone()], 1
+        taken, running = [0] * B, list(alive)
+        while True:
+            parked, pstep = sess.parked.tolist(), sess.park_step.tolist()  # the host reads of a chunk
+            for b in list(running):
+                if parked[b]:
+                    taken[b] = int(pstep[b])
+                    running.remove(b)
+                elif cnt[b] + n_phase >= max_new_tokens:
+                    taken[b] = n_phase
+                    sess.parked[b] = 1
+                    parked[b] = 1
+                    running.remove(b)
+            if not running:
+                break
+            m = 16
+            for b in running:
+                c_next = cnt[b] + n_phase
+                ban(b, c_next)
+                m = min(m, max_new_tokens - c_next)
+                if not banned[b]:
+                    m = min(m, cmax[b] - c_next + 1)
+            parts.append(sess.generate(m).t())
+            n_phase += m
+        image_rows = [b for b in alive if parked[b] == 2]
+        phases.append((torch.cat(parts, 0), taken, [b in image_rows for b in range(B)]))
+        for b in alive:
+            cnt[b] += taken[b]
+        alive = []
+        if not image_rows:
+            break
+        buf = torch.zeros(B, V, dtype=torch.float32, device=dev)
+        for b in image_rows:
+            state = dict(cur=cur[b] + taken[b] - 1, pos=pos[b] + taken[b] - 1)
+
+            def append(embeds):
+                hidden = sess.append_block(b, embeds, start[b], state["cur"], state["pos"])
+                state["cur"] += embeds.shape[1]
+                state["pos"] += embeds.shape[1]
+                return hidden
+
+            image, logits = _image_event(model, layout, append, lambda e: synthesize(e, b, n_img[b]))
+            out_images[b].append(image)
+            buf[b].copy_(logits)
+            cur[b], pos[b], cnt[b], n_img[b] = state["cur"], state["pos"], cnt[b] + layout.block_len, n_img[b] + 1
+            if cnt[b] < max_new_tokens:
+                alive.append(b)
+                sess.set_row(b, cur[b], pos[b], parked=0)
+                ban(b, cnt[b])
+            else:
+                sess.set_row(b, cur[b], pos[b], parked=1)
+        if not alive:
+            break
+        phase += 1
+        sess.begin_phase(buf, phase)
+    seqs, poss = assemble_interleaved(prompts, phases, layout)
+    return InterleavedOutput(seqs, out_images, poss)

@@ -1391,6 +1391,94 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
                                          pad=int(pad_token_id), stopping_criteria=stopping_criteria, greedy=greedy)
 
     @torch.no_grad()
+    def generate_interleaved(self, input_ids, images=None, attention_mask=None, *, max_new_tokens, max_images=4, do_sample=False,
+                             temperature=1.0, top_k=50, top_p=1.0, eos_token_id=None, pad_token_id=None, generator=None,
+                             negative_prompt_ids=None, negative_prompt_attention_mask=None, guidance_scale=7.5,
+                             num_inference_steps=50, height=None, width=None, scheduler=None, guidance_rescale=0.0, fast=None,
+                             use_graph=True):
+        """Write a document in which the model decides where an image goes, synthesises it, looks at it and carries on writing: the
+        layout of the reference's data builder (omni/data/builders/builder_dreamllm.py:119-128,315-354: `text <dream_start> [queries]
+        <dream_end> <im_start> [<im_patch> slots] <im_end> text`, of which only <dream_start> is learned) run backwards.  The
+        reference ships no such loop; INTEGRATION.md "Interleaved generation" states the protocol.
+
+        Per row: tokens are chosen exactly as in `generate` (`dllm_sample_logits` over the whole vocabulary, greedy = top-k 1 with
+        u = 0; one Philox seed per call from `generator`); eos ends the row.  On <dream_start> -- with fewer than `max_images` images
+        so far and room for both blocks in `max_new_tokens` and `max_position_embeddings`, otherwise the id is removed from the
+        choice -- the runtime appends [<dream_start>, dream queries, <dream_end>] to the row's cache (`get_prompt_embeds`' block,
+        positions continuing the row's own), takes the queries' last hidden states as `prompt_embeds` of
+        `stable_diffusion_head.pipeline(output_type="pt")` (the SDXL head through the same call; the noise of a row's i-th image
+        comes from `generation.image_generator(seed, row, i)`, so it does not depend on the order in which a path draws the images
+        of a batch; with `guidance_scale > 1` the embeds of `negative_prompt_ids` [1 or B, S'], computed once per call), turns the image
+        into CLIP pixel values on the device (`ops.image_to_clip`: antialiased bicubic resize, centre crop, normalise -- WITHOUT the
+        8-bit quantisation of the PIL-based CLIPImageProcessor), appends [<im_start>, patch embeddings, <im_end>] and continues
+        from the logits at <im_end>.  Layout tokens count toward `max_new_tokens`.
+
+        `attention_mask`: LEFT padding.  `fast` (default: batch <= 8): `decode.InterleavedDecodeSession`, graph replays with rows
+        parking on their own (`dllm_interleave_park`); `fast=False`: the model forward re-entered per token, one row at a time.
+        -> `InterleavedOutput(sequences, images, image_positions)`: per row the unpadded prompt plus everything generated (layout
+        ids in place, the query slots holding the builder's placeholder id), its images fp32 [3, H, W] in [0, 1], and the index of
+        each <dream_start>."""
+        from . import generation
+        for name, holder in (("dream_embedding", self.model), ("clip_vision_embedding", self.model), ("stable_diffusion_head", self)):
+            if not hasattr(holder, name):
+                raise ValueError(f"generate_interleaved: the model has no `{name}` plugin")
+        if input_ids is None or input_ids.dim() != 2:
+            raise ValueError("generate_interleaved: input_ids must be [batch, seq]")
+        B, S = input_ids.shape
+        max_new_tokens, max_images = int(max_new_tokens), int(max_images)
+        if max_new_tokens <= 0:
+            raise ValueError(f"generate_interleaved: `max_new_tokens` must be positive, got {max_new_tokens}")
+        if max_images < 0:
+            raise ValueError(f"generate_interleaved: `max_images` must be >= 0, got {max_images}")
+        if do_sample and not temperature > 0:
+            raise ValueError(f"generate_interleaved: `temperature` has to be a strictly positive float when sampling, got {temperature}")
+        if not 0.0 <= float(top_p) <= 1.0:
+            raise ValueError(f"generate_interleaved: `top_p` must be in [0, 1], got {top_p}")
+        if top_k is not None and int(top_k) < 0:
+            raise ValueError(f"generate_interleaved: `top_k` must be >= 0, got {top_k}")
+        if self.config.vocab_size > 32768:
+            raise ValueError("generate_interleaved: the sampling kernel covers at most 32768 ids")
+        do_cfg = guidance_scale > 1.0
+        if do_cfg and negative_prompt_ids is None:
+            raise ValueError("generate_interleaved: `guidance_scale` > 1 (classifier-free guidance) needs `negative_prompt_ids`")
+        if do_cfg and (negative_prompt_ids.dim() != 2 or negative_prompt_ids.shape[0] not in (1, B)):
+            raise ValueError("generate_interleaved: negative_prompt_ids must be [1, seq] or [batch, seq]")
+        if fast and B > 8:
+            raise ValueError("generate_interleaved: the decode GEMV handles up to 8 sequences per step (fast=True needs batch <= 8)")
+        if attention_mask is not None:
+            if attention_mask.shape != input_ids.shape:
+                raise ValueError("generate_interleaved: attention_mask must have the shape of input_ids")
+            generation.check_left_padded(attention_mask, "generate_interleaved")
+        if eos_token_id is None:
+            eos_token_id = self.config.eos_token_id
+        if isinstance(eos_token_id, (list, tuple)):
+            if len(eos_token_id) != 1:
+                raise NotImplementedError("generate_interleaved: several eos_token_id values are not supported")
+            eos_token_id = eos_token_id[0]
+        if pad_token_id is None:
+            pad_token_id = self.config.pad_token_id if self.config.pad_token_id is not None else eos_token_id
+        if pad_token_id is None:
+            pad_token_id = 0
+        seed = self._draw_seed(generator)
+        greedy = not do_sample
+        if greedy:
+            temperature, top_k, top_p = 1.0, 1, 1.0
+        negative = None
+        if do_cfg:
+            negative = self.get_prompt_embeds(negative_prompt_ids, attention_mask=negative_prompt_attention_mask)
+
+        def synthesize(prompt_embeds, row, index):
+            neg = None if negative is None else negative[row:row + 1] if negative.shape[0] > 1 else negative
+            return self.stable_diffusion_head.pipeline(
+                height=height, width=width, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                generator=generation.image_generator(seed, row, index), prompt_embeds=prompt_embeds, negative_prompt_embeds=neg,
+                output_type="pt", guidance_rescale=guidance_rescale, scheduler=scheduler, use_graph=use_graph)
+
+        return generation.interleaved_decode(self, input_ids, max_new_tokens, max_images, float(temperature), int(top_k or 0),
+                                             float(top_p), images, attention_mask, seed, fast, use_graph, eos_token_id,
+                                             int(pad_token_id), greedy, synthesize)
+
+    @torch.no_grad()
     def loglikelihood(self, requests, *, vocab_limit=None, max_batch_tokens=8192, max_batch_rows=64, return_token_logprobs=False):
         """log p(continuation | context) of given text: what the reference's multiple-choice scorers compute per answer choice
         (omni/eval/language_eval/submission_scripts/submission_dev_{hellaswag,piqa,siqa,boolq,winogrande}.py: `model(cat(question,

@@ -1933,6 +1933,64 @@ def sample_logits(logits, temperature, top_k=0, top_p=1.0, vocab_limit=None, see
     return tok_out
 
 
+def interleave_park(tok, parked, park_step, step, eos=-1, trigger=-1, pos=None, kv_len=None, slot=None):
+    """Per-row stop of a decode session (`dllm_interleave_park`, csrc/interleave.hip), in place: a running row (`parked[b] == 0`,
+    int32) whose token `tok[b]` is `eos` / `trigger` becomes parked (1 / 2) and `park_step[b]` (int64) = the value of `step` (int64
+    device tensor [1]); with `pos` (int64), `kv_len` (int32) and `slot` (int64) given, these advance by one for the rows still
+    running.  One launch, no host read: capturable in a graph."""
+    _need_gpu(tok)
+    B = tok.numel()
+    if tok.dtype != torch.int64 or park_step.dtype != torch.int64 or parked.dtype != torch.int32 or step.dtype != torch.int64:
+        raise TypeError("interleave_park: tok / park_step / step are int64, parked is int32")
+    if parked.numel() != B or park_step.numel() != B or not (tok.is_contiguous() and parked.is_contiguous() and park_step.is_contiguous()):
+        raise ValueError("interleave_park: tok, parked and park_step must be contiguous with one entry per row")
+    state = (pos, kv_len, slot)
+    advance = any(t is not None for t in state)
+    if advance:
+        if any(t is None for t in state):
+            raise ValueError("interleave_park: pos, kv_len and slot go together")
+        if pos.dtype != torch.int64 or kv_len.dtype != torch.int32 or slot.dtype != torch.int64:
+            raise TypeError("interleave_park: pos / slot are int64, kv_len is int32")
+        if any(t.numel() != B or not t.is_contiguous() for t in state):
+            raise ValueError("interleave_park: pos, kv_len and slot must be contiguous with one entry per row")
+    check("dllm_interleave_park", _p(tok), B, -1 if eos is None else int(eos), -1 if trigger is None else int(trigger), int(advance),
+          _p(step), _p(parked), _p(park_step), _p(pos), _p(kv_len), _p(slot), _stream())
+    return parked
+
+
+def image_to_clip_geometry(height, width, size):
+    """(resized height, resized width, top, left) of the CLIP hand-off: the shorter side becomes `size`, the longer one
+    `size * long // short` (CLIPImageProcessor's shortest-edge resize), then a centred size x size crop."""
+    rh, rw = (size, size * width // height) if height <= width else (size * height // width, size)
+    return rh, rw, (rh - size) // 2, (rw - size) // 2
+
+
+def image_to_clip(image, size, mean, std, out_dtype=torch.bfloat16, signed_range=False, out=None):
+    """Decoded image [B, 3, H, W] (fp32 or bf16; in [0, 1], or in [-1, 1] as the VAE emits it with `signed_range`) -> CLIP pixel
+    values [B, 3, size, size] in `out_dtype`, one launch (`dllm_image_to_clip`, csrc/interleave.hip): clamp to [0, 1], antialiased
+    bicubic resize of the shorter side to `size`, centre crop, (v - mean) / std.  It is held to
+    `F.interpolate(v.float(), (rh, rw), mode="bicubic", antialias=True, align_corners=False)` + crop + normalise in fp32
+    (`image_to_clip_geometry`); the 8-bit quantisation of the PIL-based CLIPImageProcessor is deliberately NOT reproduced.  `out`: a
+    preallocated result (no allocation: capturable in a graph)."""
+    _need_gpu(image)
+    if image.dim() != 4 or image.shape[1] != 3:
+        raise ValueError("image_to_clip: image must be [B, 3, H, W]")
+    if image.dtype not in (torch.float32, torch.bfloat16):
+        image = image.float()
+    image = image.contiguous()
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("image_to_clip: mean and std have three entries")
+    B, _, H, W = image.shape
+    size = int(size)
+    if out is None:
+        out = torch.empty(B, 3, size, size, dtype=out_dtype, device=image.device)
+    elif tuple(out.shape) != (B, 3, size, size) or not out.is_contiguous() or out.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("image_to_clip: out must be a contiguous fp32 / bf16 [B, 3, size, size] tensor")
+    check("dllm_image_to_clip", _p(image), _p(out), B, H, W, size, _dt(image), _dt(out), int(bool(signed_range)),
+          *[float(m) for m in mean], *[float(s) for s in std], _stream())
+    return out
+
+
 # The generated length beam search divides by (an eos hypothesis, is_done): tokens generated before the candidate + BEAM_LEN_OFFSET.
 # 1 = the candidate counted (transformers' `cur_len = input_ids.shape[-1] + 1` of the decoder-only fix; INTEGRATION.md "Beam search").
 BEAM_LEN_OFFSET = 1

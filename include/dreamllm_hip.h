@@ -345,6 +345,22 @@ int dllm_score_rows(const float* logits, int64_t ld, int64_t rows, int V, const 
  * depend on the segment alone), all_greedy[n] (uint8) = every greedy flag of the segment is set (1 for an empty segment). */
 int dllm_score_segments(const float* logprob, const void* greedy, const int64_t* seg_start, int64_t n_seg, int64_t rows,
                         float* sum_logprob, void* all_greedy, void* stream);
+/* Per-row stop of a decode session (csrc/interleave.hip; INTEGRATION.md "Interleaved generation"): one launch after the token choice of
+ * a step, one thread per row, B <= 64.  parked[b] (int32): 0 running, 1 parked on eos, 2 parked on the trigger id.  A running row whose
+ * token tok[b] is eos (eos >= 0) or trigger (trigger >= 0) is parked and park_step[b] = *step, the caller's step counter as it stands
+ * at the launch (after dllm_sample_logits with step_inc: the number of tokens chosen so far, this one included); a parked row stays
+ * parked.  With advance != 0, pos[b], kv_len[b] and slot[b] of the rows still running are advanced by one: a parked row keeps its
+ * position and rewrites one cache slot until the host resumes it.  Nothing is read on the host. */
+int dllm_interleave_park(const int64_t* tok, int B, int64_t eos, int64_t trigger, int advance, const int64_t* step, int* parked,
+                         int64_t* park_step, int64_t* pos, int* kv_len, int64_t* slot, void* stream);
+/* Decoded image -> CLIP pixel values in one launch (csrc/interleave.hip).  image [B][3][H][W] (in_dtype: DLLM_BF16 / DLLM_F32,
+ * contiguous), in [-1, 1] (signed_range != 0: v = x / 2 + 0.5) or [0, 1]; v is clamped to [0, 1], resized with the antialiased bicubic
+ * filter of torch's interpolate(mode="bicubic", antialias=True, align_corners=False) so that the shorter side becomes `size` (the longer
+ * one: size * long / short, truncated), centre-cropped to size x size (offset (resized - size) / 2, truncated) and normalised per
+ * channel, (v - mean) / std.  out [B][3][size][size] in out_dtype.  The PIL processor's 8-bit round trip is not reproduced.  Down-scaling
+ * factors up to about 9.9 (the taps of one 16 x 16 output tile are kept in LDS); beyond that DLLM_ERR_SHAPE. */
+int dllm_image_to_clip(const void* image, void* out, int B, int H, int W, int size, int in_dtype, int out_dtype, int signed_range,
+                       float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream);
 int64_t dllm_attn_decode_ws_floats(int B, int H, int D, int nsplit);
 /* row_map (int32 [B][map_ld] on device, or NULL; here and in dllm_attn_decode_rope): beam search's copy-free KV cache -- key slot j
  * of sequence b is read from cache row row_map[b * map_ld + j] (an entry outside [0, B) reads row b); a separate kernel
