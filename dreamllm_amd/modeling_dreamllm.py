@@ -90,7 +90,10 @@ class RotaryEmbedding(nn.Module):
         t = torch.arange(seq_len, device=device, dtype=torch.float32)
         if self.scaling_type == "linear":  # modeling_dreamllm.py:131-147
             t = t / self.scaling_factor
-        freqs = torch.einsum("i,j->ij", t, inv_freq)
+        # outside autocast: einsum is on autocast's low-precision list, and a first call under torch.autocast(bf16) (the VQA
+        # evaluation's generate()) cached bf16 tables that the RoPE kernels then read as fp32
+        with torch.autocast(device_type=torch.device(device).type, enabled=False):
+            freqs = torch.einsum("i,j->ij", t, inv_freq)
         return freqs.cos().contiguous(), freqs.sin().contiguous()
 
     def tables(self, seq_len, device):

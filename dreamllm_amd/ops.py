@@ -596,6 +596,13 @@ def rope_(x, cos, sin, pos=None, backward=False):
     B, S, NH, D = x.shape
     if x.stride(3) != 1 or x.stride(0) != S * x.stride(1):
         raise ValueError("rope_: x must have a uniform token stride")
+    # the kernel indexes the tables with pos[tok] or tok % S and a row pitch of D/2, unchecked
+    if cos.dtype != torch.float32 or sin.dtype != torch.float32:
+        raise ValueError(f"rope_: cos/sin must be fp32, got {cos.dtype} / {sin.dtype}")
+    if cos.dim() != 2 or cos.shape[1] * 2 != D or cos.shape != sin.shape or not (cos.is_contiguous() and sin.is_contiguous()):
+        raise ValueError(f"rope_: cos/sin must be contiguous [P, {D // 2}] tables, got {tuple(cos.shape)} / {tuple(sin.shape)}")
+    if pos is None and S > cos.shape[0]:
+        raise ValueError(f"rope_: {S} positions but the cos/sin tables hold {cos.shape[0]}")
     if pos is not None:
         pos = pos.reshape(-1) if pos.numel() == B * S else pos.expand(B, S).contiguous().view(-1)
         if pos.dtype != torch.int64:
@@ -645,7 +652,11 @@ def glu_bwd(dout, a, b, mode, da=None, db=None, act_out=None):
 def gather_rows(table, idx):
     _need_gpu(table, idx)
     _bf16(table)
+    if table.dim() != 2 or table.stride(1) != 1:
+        raise ValueError("gather_rows: table must be 2-D with a unit inner stride")
     idx = idx.reshape(-1).contiguous()
+    if idx.dtype != torch.int64:   # the kernel reads the indices as int64
+        idx = idx.long()
     n, D = idx.numel(), table.shape[1]
     out = torch.empty(n, D, dtype=table.dtype, device=table.device)
     check("dllm_gather_rows", _p(table), _p(idx), _p(out), n, D, table.stride(0), D, _stream())
@@ -656,10 +667,18 @@ def scatter_rows_(dst, idx, src):
     """dst[idx[i]] = src[i] (idx unique)."""
     _need_gpu(dst, idx, src)
     _bf16(dst, src)
+    if dst.dim() != 2 or dst.stride(1) != 1:
+        raise ValueError("scatter_rows_: dst must be 2-D with a unit inner stride")
+    if src.shape[-1] != dst.shape[1]:
+        raise ValueError(f"scatter_rows_: src rows have {src.shape[-1]} elements, dst rows {dst.shape[1]}")
     idx = idx.reshape(-1).contiguous()
+    if idx.dtype != torch.int64:   # the kernel reads the indices as int64
+        idx = idx.long()
     src2 = src.reshape(-1, src.shape[-1])
     if not src2.is_contiguous():
         src2 = src2.contiguous()
+    if src2.shape[0] < idx.numel():
+        raise ValueError(f"scatter_rows_: {idx.numel()} indices but {src2.shape[0]} source rows")
     check("dllm_scatter_rows", _p(src2), _p(idx), _p(dst), idx.numel(), dst.shape[1], src2.stride(0), dst.stride(0), _stream())
     return dst
 
@@ -807,6 +826,8 @@ def add_bcast(a, b):
     """a + b with b broadcast along the leading dims (b.numel() divides a.numel(); trailing layout identical)."""
     _need_gpu(a, b)
     _bf16(a, b)
+    if b.numel() == 0 or a.numel() % b.numel() != 0:   # the kernel would add a wrapped operand
+        raise ValueError(f"add_bcast: b ({b.numel()} elements) does not tile a ({a.numel()} elements)")
     a = a.contiguous()
     b = b.contiguous()
     out = torch.empty_like(a)
