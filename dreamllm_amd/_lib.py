@@ -54,6 +54,8 @@ SIGNATURES = {
     "dllm_image_to_clip": [c_void_p, c_void_p] + [c_int] * 7 + [c_float] * 6 + [c_void_p],
     "dllm_score_rows": [c_void_p, c_i64, c_i64, c_int] + [c_void_p] * 7 + [c_int] + [c_void_p] * 3,
     "dllm_score_segments": [c_void_p] * 3 + [c_i64, c_i64] + [c_void_p] * 3,
+    "dllm_clip_embed_head": [c_void_p, c_i64, c_i64, c_int, c_int, c_int] + [c_void_p] * 3 + [c_float, c_void_p, c_int] + [c_void_p] * 4,
+    "dllm_clip_select": [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 3 + [c_float, c_void_p, c_i64] + [c_void_p] * 4,
     "dllm_gemv_attn_combine": [c_void_p] * 4 + [c_int] * 4 + [c_i64] * 4 + [c_int, c_void_p],
     "dllm_attn_fwd": [c_void_p] * 7 + [c_int] * 6 + [c_i64] * 9 + [c_float, c_int, c_void_p],
     "dllm_attn_bwd": [c_void_p] * 12 + [c_int] * 6 + [c_i64] * 15 + [c_float, c_int, c_void_p],

@@ -563,3 +563,46 @@ def interleaved_decode(model, input_ids, max_new_tokens, max_images, temperature
         sess.begin_phase(buf, phase)
     seqs, poss = assemble_interleaved(prompts, phases, layout)
     return InterleavedOutput(seqs, out_images, poss)
+
+
+# ------------------------------------------------------------------------------------------------------- best-of-N selection
+class BestOfNOutput(NamedTuple):
+    """`DreamLLMForCausalMLM.best_of_n`: images fp32 [B, 3, H, W] in [0, 1] (the chosen image of every prompt), index int64 [B] (which
+    of the n seeds it came from), logits (a list of B fp32 tensors [n, m_b]: `logits_per_image` of prompt b's n images against its m_b
+    captions), seeds (the n seeds, in the order of `index`)."""
+    images: torch.Tensor
+    index: torch.Tensor
+    logits: list
+    seeds: list
+
+
+def check_best_of_n(prompt_ids, negative_prompt_ids, clip, caption_ids, captions_per_prompt, n, seeds, caption_attention_mask,
+                    guidance_scale):
+    """Every argument check of `best_of_n`, on the host, before any device work -> (seeds, captions_per_prompt) as lists of ints."""
+    from .clip_model import HipCLIPModel
+    if not isinstance(clip, HipCLIPModel):
+        raise ValueError(f"best_of_n: `clip` must be a HipCLIPModel, got {type(clip).__name__}")
+    if prompt_ids is None or prompt_ids.dim() != 2:
+        raise ValueError("best_of_n: prompt_ids must be [batch, seq]")
+    B = prompt_ids.shape[0]
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"best_of_n: `n` must be >= 1, got {n}")
+    seeds = list(range(42, 42 + n)) if seeds is None else [int(s) for s in seeds]
+    if len(seeds) != n:
+        raise ValueError(f"best_of_n: `seeds` holds {len(seeds)} seeds for n = {n}")
+    caps = [int(c) for c in captions_per_prompt]
+    if len(caps) != B:
+        raise ValueError(f"best_of_n: `captions_per_prompt` holds {len(caps)} entries for {B} prompts")
+    if caption_ids is None or caption_ids.dim() != 2:
+        raise ValueError("best_of_n: caption_ids must be [captions, seq]")
+    if any(c < 1 for c in caps) or sum(caps) != caption_ids.shape[0]:
+        raise ValueError(f"best_of_n: `captions_per_prompt` {caps} (every entry >= 1) must sum to the {caption_ids.shape[0]} rows of caption_ids")
+    clip._text.check_inputs(caption_ids, caption_attention_mask)
+    if guidance_scale > 1.0:
+        if negative_prompt_ids is None:
+            raise ValueError("best_of_n: `guidance_scale` > 1 (classifier-free guidance) needs `negative_prompt_ids`")
+        if negative_prompt_ids.dim() != 2 or negative_prompt_ids.shape[0] not in (1, B):
+            raise ValueError("best_of_n: negative_prompt_ids must be [1, seq] or [batch, seq]")
+    return seeds, caps
+

@@ -1482,6 +1482,58 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
                                              int(pad_token_id), greedy, synthesize)
 
     @torch.no_grad()
+    def best_of_n(self, prompt_ids, negative_prompt_ids, clip, caption_ids, captions_per_prompt, *, n=8, seeds=None,
+                  caption_attention_mask=None, prompt_attention_mask=None, negative_prompt_attention_mask=None, guidance_scale=7.5,
+                  num_inference_steps=50, height=None, width=None, scheduler=None, guidance_rescale=0.0, use_graph=True):
+        """Sample every prompt `n` times and keep the image CLIP likes best: the protocol behind the reference's text-to-image numbers
+        (omni/eval/text2img/ddp_sample_coco.py: `dreamllm_ddp_sample_coco` samples each caption set under the seeds 42 ... 49,
+        `select_image` scores the eight images against the set's captions with a `CLIPModel` and keeps the one that owns the largest
+        entry of `logits_per_image`, `argmax(logits_per_image) // logits_per_image.shape[1]`).
+
+        `prompt_ids` [B, S] / `negative_prompt_ids` [1 or B, S'] with their LEFT-padding masks as in `stable_diffusion_pipeline`; `clip`:
+        a `HipCLIPModel`; `caption_ids` [sum m_b, S''] (CLIP token ids, optionally with the right-padding `caption_attention_mask`):
+        prompt b is scored against the next `captions_per_prompt[b]` rows.  `seeds` defaults to 42 ... 42 + n - 1.  The prompt and
+        negative embeds are computed once; per seed `stable_diffusion_head.pipeline(output_type="pt",
+        generator=torch.Generator().manual_seed(seed))` runs on the graphed loop (the SDXL head through the same call), the batch goes
+        through `ops.image_to_clip` at the CLIP config's `image_size` with the processor's mean / std (the shorter side is resized to
+        that size and the centre is cropped: one square size, as in `generation.clip_pixels`); the n x B images are scored in ONE
+        `clip.select` call and the chosen image of every prompt is gathered on the device.  Every argument is checked before any
+        device work.
+
+        One deliberate difference from the reference (the one `generate_interleaved` documents): the reference writes 8-bit PNGs and
+        scores them after the PIL-based CLIPImageProcessor's resize; here the fp32 image goes straight to CLIP pixel values on the
+        device (antialiased bicubic resize, centre crop, normalise), WITHOUT the 8-bit quantisation and PIL's resampling.
+
+        -> `BestOfNOutput(images fp32 [B, 3, H, W] in [0, 1], index int64 [B], logits: list of fp32 [n, m_b], seeds)`."""
+        from . import generation
+        seeds, caps = generation.check_best_of_n(prompt_ids, negative_prompt_ids, clip, caption_ids, captions_per_prompt, n, seeds,
+                                                 caption_attention_mask, guidance_scale)
+        if not hasattr(self, "stable_diffusion_head"):
+            raise ValueError("best_of_n: the model has no `stable_diffusion_head` plugin")
+        B, n = prompt_ids.shape[0], len(seeds)
+        prompt_embeds = self.get_prompt_embeds(prompt_ids, attention_mask=prompt_attention_mask)
+        negative = None
+        if guidance_scale > 1.0:
+            negative = self.get_prompt_embeds(negative_prompt_ids, attention_mask=negative_prompt_attention_mask)
+            if negative.shape[0] != B:
+                negative = negative.expand(B, -1, -1)
+        images, pixels = [], []
+        for seed in seeds:
+            image = self.stable_diffusion_head.pipeline(
+                height=height, width=width, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                generator=torch.Generator().manual_seed(seed), prompt_embeds=prompt_embeds, negative_prompt_embeds=negative,
+                output_type="pt", guidance_rescale=guidance_rescale, scheduler=scheduler, use_graph=use_graph)
+            images.append(image)
+            pixels.append(ops.image_to_clip(image, clip.image_size, clip.image_mean, clip.image_std, out_dtype=clip.dtype))
+        images = torch.stack(images, 1)                                   # [B, n, 3, H, W]: prompt b's images are one group
+        pixels = torch.stack(pixels, 1).flatten(0, 1)
+        dev = pixels.device
+        sel = clip.select(pixels, caption_ids.to(dev), [n] * B, caps,
+                          attention_mask=None if caption_attention_mask is None else caption_attention_mask.to(dev))
+        chosen = images[torch.arange(B, device=images.device), sel.best.to(images.device)]
+        return generation.BestOfNOutput(chosen, sel.best, sel.logits, seeds)
+
+    @torch.no_grad()
     def loglikelihood(self, requests, *, vocab_limit=None, max_batch_tokens=8192, max_batch_rows=64, return_token_logprobs=False):
         """log p(continuation | context) of given text: what the reference's multiple-choice scorers compute per answer choice
         (omni/eval/language_eval/submission_scripts/submission_dev_{hellaswag,piqa,siqa,boolq,winogrande}.py: `model(cat(question,

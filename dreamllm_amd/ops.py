@@ -2012,6 +2012,92 @@ def image_to_clip(image, size, mean, std, out_dtype=torch.bfloat16, signed_range
     return out
 
 
+ClipEmbed = collections.namedtuple("ClipEmbed", "embeds raw status")
+ClipSelect = collections.namedtuple("ClipSelect", "best best_logit logits out_start status")
+
+
+def clip_embed_head(hidden, pos, ln_w, ln_b, eps, proj, *, want_raw=False, status=None):
+    """The pooled tail of a CLIP tower in one launch (`dllm_clip_embed_head`, semantics in csrc/clip_score.hip): row `pos[b]` (int64 [B]
+    on the device, clamped to the sequence; None: row 0, the vision CLS token) of the bf16 `hidden` [B, S, H] (any batch / sequence
+    strides, H contiguous, H % 8 == 0, H <= 2048) -> LayerNorm(`ln_w`, `ln_b`, `eps`) kept in fp32 -> `proj` (bf16 [P, H], no bias) ->
+    `ClipEmbed(embeds fp32 [B, P] of unit L2 norm, raw fp32 [B, P] before the normalisation (`want_raw`, else None), status int32 [B])`;
+    a row whose norm is zero or not finite is all zeros with status 1 (OR-ed into `status` if one is passed)."""
+    _need_gpu(hidden, ln_w, ln_b, proj, pos)
+    _bf16(hidden, ln_w, ln_b, proj)
+    if hidden.dim() != 3 or proj.dim() != 2 or ln_w.dim() != 1 or ln_b.dim() != 1:
+        raise ValueError("clip_embed_head: hidden [B, S, H], ln_w / ln_b [H], proj [P, H]")
+    B, S, H = hidden.shape
+    P = proj.shape[0]
+    if proj.shape[1] != H or ln_w.numel() != H or ln_b.numel() != H:
+        raise ValueError(f"clip_embed_head: ln_w {tuple(ln_w.shape)}, ln_b {tuple(ln_b.shape)}, proj {tuple(proj.shape)} do not match H = {H}")
+    if pos is not None and (pos.dtype != torch.int64 or pos.dim() != 1 or pos.numel() != B):
+        raise ValueError("clip_embed_head: pos must be int64 [B]")
+    dev = hidden.device
+    if hidden.stride(2) != 1 or hidden.stride(0) % 8 or hidden.stride(1) % 8 or hidden.data_ptr() % 16:
+        hidden = hidden.contiguous()     # 16-byte rows for the kernel's vector loads
+    ln_w, ln_b, proj = ln_w.contiguous(), ln_b.contiguous(), proj.contiguous()
+    pos = None if pos is None else pos.contiguous()
+    if status is None:
+        status = torch.zeros(B, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.numel() != B or status.device != dev or not status.is_contiguous():
+        raise TypeError("clip_embed_head: status must be a contiguous int32 [B] tensor on the hidden states' device")
+    embeds = torch.empty(B, P, dtype=torch.float32, device=dev)
+    raw = torch.empty(B, P, dtype=torch.float32, device=dev) if want_raw else None
+    check("dllm_clip_embed_head", _p(hidden), hidden.stride(0), hidden.stride(1), B, S, H, _p(pos), _p(ln_w), _p(ln_b), float(eps),
+          _p(proj), P, _p(embeds), _p(raw), _p(status), _stream())
+    return ClipEmbed(embeds, raw, status)
+
+
+def clip_group_starts(images_per_group, captions_per_group):
+    """Host plan of `clip_select`: the group sizes (Python ints) -> (img_start, txt_start, out_start) as lists of G + 1 ints; every
+    failure is a ValueError before any launch."""
+    n, m = [int(v) for v in images_per_group], [int(v) for v in captions_per_group]
+    if len(n) != len(m):
+        raise ValueError(f"clip_select: {len(n)} image groups but {len(m)} caption groups")
+    for g, (a, b) in enumerate(zip(n, m)):
+        if a < 1 or b < 1:
+            raise ValueError(f"clip_select: group {g} is empty ({a} images, {b} captions)")
+    si, st, so = [0], [0], [0]
+    for a, b in zip(n, m):
+        si.append(si[-1] + a)
+        st.append(st[-1] + b)
+        so.append(so[-1] + a * b)
+    if so[-1] > 0x7FFFFFFF:
+        raise ValueError("clip_select: more than 2^31 - 1 logits")
+    return si, st, so
+
+
+def clip_select(img, txt, images_per_group, captions_per_group, scale, *, want_logits=True, status=None):
+    """Scaled similarities and the best image of every group in one launch (`dllm_clip_select`, semantics in csrc/clip_score.hip).
+    `img` fp32 [NI, D] and `txt` fp32 [NT, D] hold unit rows (`clip_embed_head`; D % 4 == 0); group g owns the next
+    `images_per_group[g]` images and `captions_per_group[g]` captions (Python ints, all >= 1, summing to NI / NT).  ->
+    `ClipSelect(best int64 [G] (index within the group of the image that owns the largest logit; ties: the lowest flat index, as
+    torch.argmax), best_logit fp32 [G], logits fp32 [sum n m] (group g row-major [n, m] at out_start[g]; None without `want_logits`),
+    out_start (list of G + 1 ints), status int32 [G] (1: the group held a NaN / infinite logit, ranked below every finite one))`."""
+    si, st, so = clip_group_starts(images_per_group, captions_per_group)
+    if img.dim() != 2 or txt.dim() != 2 or img.shape[1] != txt.shape[1]:
+        raise ValueError("clip_select: img [NI, D] and txt [NT, D]")
+    if si[-1] != img.shape[0] or st[-1] != txt.shape[0]:
+        raise ValueError(f"clip_select: the groups hold {si[-1]} images and {st[-1]} captions, the embeddings {img.shape[0]} and {txt.shape[0]}")
+    _need_gpu(img, txt)
+    if img.dtype != torch.float32 or txt.dtype != torch.float32:
+        raise TypeError("clip_select expects fp32 embeddings")
+    img, txt = img.contiguous(), txt.contiguous()
+    dev = img.device
+    G = len(si) - 1
+    starts = torch.tensor([si, st, so], dtype=torch.int32).to(dev)
+    if status is None:
+        status = torch.zeros(G, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.numel() != G or status.device != dev or not status.is_contiguous():
+        raise TypeError("clip_select: status must be a contiguous int32 [G] tensor on the embeddings' device")
+    logits = torch.empty(so[-1], dtype=torch.float32, device=dev) if want_logits else None
+    best = torch.empty(G, dtype=torch.int64, device=dev)
+    best_logit = torch.empty(G, dtype=torch.float32, device=dev)
+    check("dllm_clip_select", _p(img), _p(txt), img.shape[0], txt.shape[0], img.shape[1], G, _p(starts[0]), _p(starts[1]), _p(starts[2]),
+          float(scale), _p(logits), so[-1], _p(best), _p(best_logit), _p(status), _stream())
+    return ClipSelect(best, best_logit, logits, so, status)
+
+
 # The generated length beam search divides by (an eos hypothesis, is_done): tokens generated before the candidate + BEAM_LEN_OFFSET.
 # 1 = the candidate counted (transformers' `cur_len = input_ids.shape[-1] + 1` of the decoder-only fix; INTEGRATION.md "Beam search").
 BEAM_LEN_OFFSET = 1

@@ -345,6 +345,25 @@ int dllm_score_rows(const float* logits, int64_t ld, int64_t rows, int V, const 
  * depend on the segment alone), all_greedy[n] (uint8) = every greedy flag of the segment is set (1 for an empty segment). */
 int dllm_score_segments(const float* logprob, const void* greedy, const int64_t* seg_start, int64_t n_seg, int64_t rows,
                         float* sum_logprob, void* all_greedy, void* stream);
+/* CLIP text-image scoring (csrc/clip_score.hip; omni/eval/text2img/ddp_sample_coco.py `select_image` over transformers [ext]
+ * `CLIPModel`; rules in INTEGRATION.md "Best-of-N selection").
+ * dllm_clip_embed_head: the pooled tail of a CLIP tower, one block per row b.  hidden bf16 [B][S][H] (element strides sb, ss, multiples
+ * of 8; H contiguous, H % 8 == 0, H <= 2048), row r = clamp(pos[b], 0, S - 1) (pos int64 [B]; NULL: row 0, the vision CLS token):
+ * y = LayerNorm(fp32(hidden[b][r]), ln_w, ln_b, eps) with a two-pass fp32 variance, y kept in fp32; e_p = sum_k proj[p][k] y_k (proj bf16
+ * [P][H], no bias); raw[b][p] = e_p (fp32 [B][P], optional), embeds[b][p] = e_p / ||e|| (fp32 [B][P]).  A row whose squared norm is zero
+ * or not finite writes zeros and sets status[b] = 1 (int32 [B], optional, never cleared).  B == 0: nothing to do.
+ * dllm_clip_select: one block per group g < G of images [img_start[g], img_start[g + 1]) (n of them) and texts [txt_start[g],
+ * txt_start[g + 1]) (m of them; int32 [G + 1] on the device, clamped to [0, NI] / [0, NT]).  img fp32 [NI][D], txt fp32 [NT][D] (unit
+ * rows, not renormalised; D % 4 == 0, 16-byte aligned): logits[out_start[g] + i m + j] = scale <img_i, txt_j> (fp32 [n_logits], optional;
+ * a group that does not fit writes none and sets status bit 1); best[g] (int64) = (lowest flat index i m + j of the largest finite
+ * logit) / m = torch.argmax's first occurrence // m; best_logit[g] that logit.  A NaN or an infinity ranks below every finite logit and
+ * sets status[g] |= 1 (int32 [G], optional, never cleared); no finite logit: best 0, best_logit NaN.
+ * Both deterministic: fixed-order sums, no float atomics. */
+int dllm_clip_embed_head(const void* hidden, int64_t sb, int64_t ss, int B, int S, int H, const int64_t* pos, const void* ln_w,
+                         const void* ln_b, float eps, const void* proj, int P, float* embeds, float* raw, int* status, void* stream);
+int dllm_clip_select(const float* img, const float* txt, int NI, int NT, int D, int G, const int* img_start, const int* txt_start,
+                     const int* out_start, float scale, float* logits, int64_t n_logits, int64_t* best, float* best_logit, int* status,
+                     void* stream);
 /* Per-row stop of a decode session (csrc/interleave.hip; INTEGRATION.md "Interleaved generation"): one launch after the token choice of
  * a step, one thread per row, B <= 64.  parked[b] (int32): 0 running, 1 parked on eos, 2 parked on the trigger id.  A running row whose
  * token tok[b] is eos (eos >= 0) or trigger (trigger >= 0) is parked and park_step[b] = *step, the caller's step counter as it stands
