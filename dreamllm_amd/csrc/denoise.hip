@@ -21,6 +21,8 @@
 // Same two forms; +16 B read and +16 B written per pixel.
 #include "common.h"
 
+#include <type_traits>
+
 namespace {
 
 constexpr int SCHED_THREADS = 256;
@@ -89,15 +91,6 @@ __device__ __forceinline__ void update(const SchedArgs& a, int64_t i, f32x4 e) {
         for (int g = 0; g < a.G; ++g) st_bf16x8(a.next_in + (g * a.B * a.P + i) * 8, o);
 }
 
-__global__ __launch_bounds__(SCHED_THREADS) void cfg_sched_kernel(SchedArgs a) {
-    const int64_t n = a.B * a.P;
-    for (int64_t i = (int64_t)blockIdx.x * SCHED_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * SCHED_THREADS) {
-        f32x4 e, ec;
-        guided(a, i, e, ec);
-        update(a, i, e);
-    }
-}
-
 // multistep update of pixel i from its guided (and rescaled) prediction; hist: m1 in (only when it has a weight), m0 out
 __device__ __forceinline__ void update(const DpmArgs& a, int64_t i, f32x4 e) {
     f32x4 x = *reinterpret_cast<f32x4*>(a.lat + i * 4);
@@ -118,7 +111,9 @@ __device__ __forceinline__ void update(const DpmArgs& a, int64_t i, f32x4 e) {
         for (int g = 0; g < a.G; ++g) st_bf16x8(a.next_in + (g * a.B * a.P + i) * 8, o);
 }
 
-__global__ __launch_bounds__(SCHED_THREADS) void cfg_dpm_kernel(DpmArgs a) {
+// one thread per latent pixel, grid-stride
+template <typename Args>
+__global__ __launch_bounds__(SCHED_THREADS) void cfg_step_kernel(Args a) {
     const int64_t n = a.B * a.P;
     for (int64_t i = (int64_t)blockIdx.x * SCHED_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * SCHED_THREADS) {
         f32x4 e, ec;
@@ -143,7 +138,9 @@ __device__ __forceinline__ f32x2 block_sum2(f32x2 v, f32x2* red) {
     return s;
 }
 
-__global__ __launch_bounds__(RESCALE_THREADS) void cfg_sched_rescale_kernel(SchedArgs a) {
+// one block per image, three passes (verified: each instantiation compiles to the instruction stream and registers of a hand-written copy)
+template <typename Args>
+__global__ __launch_bounds__(RESCALE_THREADS) void cfg_step_rescale_kernel(Args a) {
     __shared__ f32x2 red[RESCALE_WAVES];
     const int64_t base = (int64_t)blockIdx.x * a.P;
     const float cnt = (float)(a.P * 4);
@@ -180,88 +177,13 @@ __global__ __launch_bounds__(RESCALE_THREADS) void cfg_sched_rescale_kernel(Sche
     }
 }
 
-// the same three passes around the multistep update (a copy, not a shared template: factoring the passes out of the kernel above
-// changes its register allocation, and its generated code is meant to stay as it is)
-__global__ __launch_bounds__(RESCALE_THREADS) void cfg_dpm_rescale_kernel(DpmArgs a) {
-    __shared__ f32x2 red[RESCALE_WAVES];
-    const int64_t base = (int64_t)blockIdx.x * a.P;
-    const float cnt = (float)(a.P * 4);
-    // pass 1: means of the conditional prediction and of the guided one
-    f32x2 s = {0.f, 0.f};
-    for (int64_t p = threadIdx.x; p < a.P; p += RESCALE_THREADS) {
-        f32x4 e, ec;
-        guided(a, base + p, e, ec);
-        s[0] += (ec[0] + ec[1]) + (ec[2] + ec[3]);
-        s[1] += (e[0] + e[1]) + (e[2] + e[3]);
-    }
-    const f32x2 mean = block_sum2(s, red) / cnt;
-    // pass 2: centred sums of squares
-    f32x2 q = {0.f, 0.f};
-    for (int64_t p = threadIdx.x; p < a.P; p += RESCALE_THREADS) {
-        f32x4 e, ec;
-        guided(a, base + p, e, ec);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float dc = ec[k] - mean[0], de = e[k] - mean[1];
-            q[0] += dc * dc;
-            q[1] += de * de;
-        }
-    }
-    const f32x2 ss = block_sum2(q, red);
-    const float ratio = sqrtf(ss[0] / (cnt - 1.f)) / sqrtf(ss[1] / (cnt - 1.f));  // std(e_c) / std(e)
-    // pass 3: rescale + update
-    for (int64_t p = threadIdx.x; p < a.P; p += RESCALE_THREADS) {
-        f32x4 e, ec;
-        guided(a, base + p, e, ec);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) e[k] = a.phi * (e[k] * ratio) + (1.f - a.phi) * e[k];
-        update(a, base + p, e);
-    }
-}
-
-}  // namespace
-
-extern "C" int dllm_cfg_sched_step(const void* pred, float* latents, const float* noise, void* next_in, int64_t B, int64_t P, int G,
-                                   float guidance, float rescale, int v_prediction, float sqrt_at, float sqrt_1mat, float k_x0,
-                                   float k_eps, float k_x, float sigma, void* stream) {
-    if (B < 0 || P < 0 || B > 0x7FFFFFFFLL || (G != 1 && G != 2) || !(rescale >= 0.f) || (rescale > 0.f && P * 4 < 2))
-        return DLLM_ERR_SHAPE;
-    if (B == 0 || P == 0) return DLLM_OK;
-    if (pred == nullptr || latents == nullptr || (sigma != 0.f && noise == nullptr)) return DLLM_ERR_SHAPE;
-    if (reinterpret_cast<uintptr_t>(pred) & 7 || reinterpret_cast<uintptr_t>(latents) & 15 ||
-        reinterpret_cast<uintptr_t>(noise) & 15 || reinterpret_cast<uintptr_t>(next_in) & 15)
-        return DLLM_ERR_ALIGN;
-    SchedArgs a;
-    a.pred = (const bf16*)pred;
-    a.lat = latents;
-    a.noise = noise;
-    a.next_in = (bf16*)next_in;
-    a.B = B;
-    a.P = P;
-    a.G = G;
-    a.vpred = v_prediction ? 1 : 0;
-    a.gs = guidance;
-    a.phi = rescale;
-    a.sa = sqrt_at;
-    a.s1a = sqrt_1mat;
-    a.k_x0 = k_x0;
-    a.k_eps = k_eps;
-    a.k_x = k_x;
-    a.sigma = sigma;
-    hipStream_t s = (hipStream_t)stream;
-    if (rescale > 0.f) {
-        hipLaunchKernelGGL(cfg_sched_rescale_kernel, dim3((unsigned)B), dim3(RESCALE_THREADS), 0, s, a);
-    } else {
-        int64_t g = cdiv64(B * P, SCHED_THREADS);
-        if (g > 8192) g = 8192;  // grid-stride the rest
-        hipLaunchKernelGGL(cfg_sched_kernel, dim3((unsigned)g), dim3(SCHED_THREADS), 0, s, a);
-    }
-    return dllm_check_launch();
-}
-
-extern "C" int dllm_cfg_dpm_step(const void* pred, float* latents, float* hist, const float* noise, void* next_in, int64_t B, int64_t P,
-                                 int G, float guidance, float rescale, int v_prediction, float sqrt_at, float sqrt_1mat, float k_x,
-                                 float k_m0, float k_m1, float sigma, void* stream) {
+// What the two entry points share: the argument checks, the common fields, and the launch -- with rescale one block per image, else
+// grid-stride capped at 8192 blocks.  `a` arrives with the scheduler's own fields set (for DpmArgs that includes hist).
+template <typename Args>
+int cfg_step(Args& a, const void* pred, float* latents, const float* noise, void* next_in, int64_t B, int64_t P, int G, float guidance,
+             float rescale, int v_prediction, float sqrt_at, float sqrt_1mat, float sigma, void* stream) {
+    const float* hist = latents;  // no history: nothing more to check
+    if constexpr (std::is_same_v<Args, DpmArgs>) hist = a.hist;
     if (B < 0 || P < 0 || B > 0x7FFFFFFFLL || (G != 1 && G != 2) || !(rescale >= 0.f) || (rescale > 0.f && P * 4 < 2))
         return DLLM_ERR_SHAPE;
     if (B == 0 || P == 0) return DLLM_OK;
@@ -269,10 +191,8 @@ extern "C" int dllm_cfg_dpm_step(const void* pred, float* latents, float* hist, 
     if (reinterpret_cast<uintptr_t>(pred) & 7 || reinterpret_cast<uintptr_t>(latents) & 15 || reinterpret_cast<uintptr_t>(hist) & 15 ||
         reinterpret_cast<uintptr_t>(noise) & 15 || reinterpret_cast<uintptr_t>(next_in) & 15)
         return DLLM_ERR_ALIGN;
-    DpmArgs a;
     a.pred = (const bf16*)pred;
     a.lat = latents;
-    a.hist = hist;
     a.noise = noise;
     a.next_in = (bf16*)next_in;
     a.B = B;
@@ -283,17 +203,37 @@ extern "C" int dllm_cfg_dpm_step(const void* pred, float* latents, float* hist, 
     a.phi = rescale;
     a.sa = sqrt_at;
     a.s1a = sqrt_1mat;
-    a.k_x = k_x;
-    a.k_m0 = k_m0;
-    a.k_m1 = k_m1;
     a.sigma = sigma;
     hipStream_t s = (hipStream_t)stream;
     if (rescale > 0.f) {
-        hipLaunchKernelGGL(cfg_dpm_rescale_kernel, dim3((unsigned)B), dim3(RESCALE_THREADS), 0, s, a);
+        hipLaunchKernelGGL(cfg_step_rescale_kernel<Args>, dim3((unsigned)B), dim3(RESCALE_THREADS), 0, s, a);
     } else {
         int64_t g = cdiv64(B * P, SCHED_THREADS);
         if (g > 8192) g = 8192;  // grid-stride the rest
-        hipLaunchKernelGGL(cfg_dpm_kernel, dim3((unsigned)g), dim3(SCHED_THREADS), 0, s, a);
+        hipLaunchKernelGGL(cfg_step_kernel<Args>, dim3((unsigned)g), dim3(SCHED_THREADS), 0, s, a);
     }
     return dllm_check_launch();
+}
+
+}  // namespace
+
+extern "C" int dllm_cfg_sched_step(const void* pred, float* latents, const float* noise, void* next_in, int64_t B, int64_t P, int G,
+                                   float guidance, float rescale, int v_prediction, float sqrt_at, float sqrt_1mat, float k_x0,
+                                   float k_eps, float k_x, float sigma, void* stream) {
+    SchedArgs a;
+    a.k_x0 = k_x0;
+    a.k_eps = k_eps;
+    a.k_x = k_x;
+    return cfg_step(a, pred, latents, noise, next_in, B, P, G, guidance, rescale, v_prediction, sqrt_at, sqrt_1mat, sigma, stream);
+}
+
+extern "C" int dllm_cfg_dpm_step(const void* pred, float* latents, float* hist, const float* noise, void* next_in, int64_t B, int64_t P,
+                                 int G, float guidance, float rescale, int v_prediction, float sqrt_at, float sqrt_1mat, float k_x,
+                                 float k_m0, float k_m1, float sigma, void* stream) {
+    DpmArgs a;
+    a.hist = hist;
+    a.k_x = k_x;
+    a.k_m0 = k_m0;
+    a.k_m1 = k_m1;
+    return cfg_step(a, pred, latents, noise, next_in, B, P, G, guidance, rescale, v_prediction, sqrt_at, sqrt_1mat, sigma, stream);
 }

@@ -18,49 +18,13 @@ import torch
 from torch import nn
 
 from . import ops
+from .denoising import decode_output, denoise, graph_denoise_mode, predraw_step_noise  # noqa: F401 (the last two: importable from here)
 from .projector import build_projector
 from . import utils as _u
 from .utils import FSDPMixin, check_path_and_file, get_model_device, get_model_dtype, logger, randn_tensor
 
 PluginType = Literal["embedding", "head"]
 PipelineImageType = Any
-
-
-def graph_denoise_mode(use_graph, sched, guidance_scale, guidance_rescale, eta, callback, num_images_per_prompt, in_channels):
-    """Which denoising loop `pipeline` runs (both heads; host logic only):
-      "ddim"  -- deterministic DDIM + CFG, no rescale, no callback: hipGraph replay + `dllm_cfg_ddim_step` (the original fast path);
-      "sched" -- any scheduler with `step_coeffs` (DDPM, DDIM with eta), with or without CFG / rescale / callback: hipGraph replay +
-                 `dllm_cfg_sched_step`;
-      "multistep" -- a scheduler with `multistep_coeffs` (DPM-Solver++), same freedom: hipGraph replay + `dllm_cfg_dpm_step`, the
-                 previous step's data prediction kept in a device buffer;
-      None    -- the plain per-step loop (`use_graph=False`, a scheduler with neither `step_coeffs` nor `multistep_coeffs`,
-                 num_images_per_prompt != 1, an inpainting-style UNet)."""
-    if not (use_graph and num_images_per_prompt == 1 and in_channels == 4):
-        return None
-    if (guidance_scale > 1.0 and guidance_rescale == 0.0 and eta == 0.0 and hasattr(sched, "step_cfg_fused_")
-            and callback is None):
-        return "ddim"
-    if hasattr(sched, "step_coeffs"):
-        return "sched"
-    return "multistep" if hasattr(sched, "multistep_coeffs") else None
-
-
-def predraw_step_noise(shape, coeffs, generator, device):
-    """The plain loop's ancestral draws, made ahead of a graphed loop: one `randn_tensor(shape, generator, device, fp32)` (NCHW, as
-    `scheduler.step` draws it) per step whose coefficients draw, in step order -> fp32 [n, B, H, W, C] (NHWC) on `device`, or None
-    when no step draws.  Seeded CPU generators, lists of generators, `generator=None` (the device's default generator: the UNet
-    draws nothing) and `utils.replay_draws` give the plain loop's values bit for bit."""
-    n = sum(1 for c in coeffs if c.draws)
-    if n == 0:
-        return None
-    B, C, H, W = shape
-    out = torch.empty(n, B, H, W, C, dtype=torch.float32, device=device)
-    k = 0
-    for c in coeffs:
-        if c.draws:
-            out[k].copy_(randn_tensor(shape, generator=generator, device=device, dtype=torch.float32).permute(0, 2, 3, 1))
-            k += 1
-    return out
 
 
 class PluginBase(ABC, nn.Module, FSDPMixin):
@@ -439,6 +403,22 @@ class StableDiffusionHead(MultimodalHead):
         timesteps = timesteps.long()
         return latents, noise, timesteps, self.noise_scheduler.add_noise(latents, new_noise, timesteps)
 
+    def _diffusion_loss(self, model_pred, latents, noise, timesteps):
+        """modeling_plugins.py:538-575: the prediction type's target, MSE, optionally min-SNR weighted per sample."""
+        if self.noise_scheduler.config.prediction_type == "epsilon":
+            target = noise
+        elif self.noise_scheduler.config.prediction_type == "v_prediction":
+            target = self.noise_scheduler.get_velocity(latents, noise, timesteps)
+        else:
+            raise ValueError(f"Unknown prediction type {self.noise_scheduler.config.prediction_type}")
+        if self.snr_gamma is None:
+            return ops.mse_loss(model_pred, target.float())
+        snr = self._compute_snr(timesteps)
+        if self.noise_scheduler.config.prediction_type == "v_prediction":
+            snr = snr + 1
+        w = torch.stack([snr, self.snr_gamma * torch.ones_like(snr)], dim=1).min(dim=1)[0] / snr
+        return (ops.mse_loss_per_sample(model_pred, target.float()) * w).mean()
+
     def forward(self, images=None, encoder_hidden_states=None, u_encoder_hidden_states=None, dream_embeddings=None,
                 noise=None, timesteps=None):
         """modeling_plugins.py:493-577.  `noise` / `timesteps` may be injected (tests, reproducible benchmarks); when
@@ -459,24 +439,8 @@ class StableDiffusionHead(MultimodalHead):
             encoder_hidden_states = (1.0 - mask) * encoder_hidden_states + mask * u_encoder_hidden_states
 
         encoder_hidden_states = self.projector(encoder_hidden_states)[-1]
-        if self.noise_scheduler.config.prediction_type == "epsilon":
-            target = noise
-        elif self.noise_scheduler.config.prediction_type == "v_prediction":
-            target = self.noise_scheduler.get_velocity(latents, noise, timesteps)
-        else:
-            raise ValueError(f"Unknown prediction type {self.noise_scheduler.config.prediction_type}")
-
         model_pred = self.unet(noisy_latents, timesteps, encoder_hidden_states).sample
-        if self.snr_gamma is None:
-            loss = ops.mse_loss(model_pred, target.float())
-        else:
-            snr = self._compute_snr(timesteps)
-            if self.noise_scheduler.config.prediction_type == "v_prediction":
-                snr = snr + 1
-            w = torch.stack([snr, self.snr_gamma * torch.ones_like(snr)], dim=1).min(dim=1)[0] / snr
-            per = ops.mse_loss_per_sample(model_pred, target.float())
-            loss = (per * w).mean()
-        return loss
+        return self._diffusion_loss(model_pred, latents, noise, timesteps)
 
     # ---- inference pipeline ------------------------------------------------------------------------------------
     def check_inputs(self, height, width, callback_steps, prompt_embeds=None, negative_prompt_embeds=None):
@@ -515,106 +479,16 @@ class StableDiffusionHead(MultimodalHead):
         noise_pred_rescaled = noise_cfg * (std_text / std_cfg)
         return guidance_rescale * noise_pred_rescaled + (1 - guidance_rescale) * noise_cfg
 
-    @torch.no_grad()
-    def _denoise_loop_graph(self, latents, ctx_embeds, timesteps, sched, guidance_scale, added_cond_kwargs=None, mode="ddim",
-                            guidance_rescale=0.0, eta=0.0, generator=None, callback=None, callback_steps=1):
-        """The loop body (modeling_plugins.py:809-839) as: [fill t] -> hipGraph replay of one UNet forward on static NHWC
-        buffers -> ONE fused kernel (CFG combine + scheduler update + next UNet input).  ~600 kernel launches per step collapse
-        into one graph launch, which is what the loop is bound by at B_img = 1.  The graph (and its static buffers, including
-        the cross-attention K/V of the conditioning tokens) is cached per shape and CFG factor G.
-        mode "ddim" (see `graph_denoise_mode`): deterministic DDIM + CFG through `dllm_cfg_ddim_step`.  mode "sched": any
-        scheduler with `step_coeffs`, CFG (G = 2) or not (G = 1, the UNet captured at batch B), guidance rescale, ancestral noise
-        drawn ahead of the loop in the plain loop's order (`predraw_step_noise`), `callback(i, t, latents)` as the plain loop.
-        mode "multistep": the same for a scheduler with `multistep_coeffs`, through `dllm_cfg_dpm_step`; the history buffer (the
-        previous step's data prediction) is allocated here, per call.  The captured graph is the same one for every mode."""
-        B, C, H, W = latents.shape
-        do_cfg = guidance_scale > 1.0
-        G = 2 if (mode == "ddim" or do_cfg) else 1
-        key = (B, H, W, tuple(ctx_embeds.shape), added_cond_kwargs is not None, G)
-        cache = getattr(self, "_graph_cache", None)
-        if cache is None:
-            cache = self._graph_cache = {}
-        dev = latents.device
-        ent = cache.get(key)
-        ctx_now = self.unet.prepare_context(ctx_embeds)
-        # everything that depends on the timestep only (sinusoid, time-embedding MLP, every ResBlock's time_emb_proj: ~38 tiny
-        # launches per step) is computed for ALL steps here, one GEMM per ResBlock; the captured forward reads one row of it
-        addk = None if added_cond_kwargs is None else {k: v.to(dev) for k, v in added_cond_kwargs.items()}
-        # ONE host conversion of the schedule (a device tensor would cost a sync per element); without micro-conditioning the table
-        # depends on (schedule, batch) only and is kept across calls (ADVICE r03)
-        ts_host = tuple(float(t) for t in (timesteps.tolist() if torch.is_tensor(timesteps) else timesteps))
-        # every parameter the table is computed from -- time-embedding MLP, each ResBlock's time_emb_proj weight AND bias -- with its
-        # storage pointer, dtype and device beside identity / version: `module.to()` swaps `.data` without touching either (ADVICE r04)
-        def _sig(p):
-            return (id(p), p._version, p.data_ptr(), p.dtype, str(p.device))
-        w_sig = tuple(_sig(p) for p in self.unet.time_embedding.parameters()) + \
-            tuple(_sig(p) for r in self.unet._resnets() for p in r.time_emb_proj.parameters())
-        tb_key = (ts_host, G * B, w_sig)
-        tb_cache = getattr(self, "_time_bias_cache", None)
-        if addk is None and tb_cache is not None and tb_cache[0] == tb_key:
-            tb_table = tb_cache[1]
-        else:
-            tb_table = self.unet.precompute_time_bias(list(ts_host), G * B, addk)
-            self._time_bias_cache = (tb_key, tb_table) if addk is None else None
-        if ent is None:
-            x_in = torch.zeros(G * B, H, W, 8, dtype=self.dtype, device=dev)
-            tb_static = tb_table[0].clone()
-            ctx_static = {k: [t.clone() for t in v] for k, v in ctx_now.items()}
-            emb_static = ctx_embeds.clone()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # warm-up outside capture (lazy caches, kernel attributes)
-                for _ in range(2):
-                    self.unet(x_in, None, emb_static, context_cache=ctx_static, nhwc_io=True, return_dict=False, time_bias=tb_static)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            # capture ON the warm-up stream: the per-(device, stream) buffers of the operators (GroupNorm meeting slots, stream-K
-            # workspace, split-K counters) were allocated by the warm-up calls above, outside the capture -- a different capture
-            # stream would allocate new ones from the graph's private pool (ADVICE r03)
-            with torch.cuda.graph(graph, stream=side):
-                pred = self.unet(x_in, None, emb_static, context_cache=ctx_static, nhwc_io=True, return_dict=False,
-                                 time_bias=tb_static)[0]
-            ent = cache[key] = dict(graph=graph, x_in=x_in, tb=tb_static, ctx=ctx_static, pred=pred, stream=side)  # (keeps the stream's handle alive)
-        for k, v in ctx_now.items():
-            for dst, src in zip(ent["ctx"][k], v):
-                dst.copy_(src)
-        lat = latents.permute(0, 2, 3, 1).contiguous().float()  # NHWC fp32 master copy
-        x_in = ent["x_in"]
-        x_in.zero_()
-        for g in range(G):
-            x_in[g * B:(g + 1) * B, ..., :4] = lat.to(self.dtype)
-        if mode == "ddim":
-            for i, t in enumerate(ts_host):  # host floats: no per-step device read of the schedule
-                ent["tb"].copy_(tb_table[i])
-                ent["graph"].replay()
-                sched.step_cfg_fused_(ent["pred"], t, lat, x_in, guidance_scale)
-            return lat.permute(0, 3, 1, 2).contiguous()
-        if sched.config.prediction_type not in ("epsilon", "v_prediction"):
-            raise ValueError(sched.config.prediction_type)
-        vpred = sched.config.prediction_type == "v_prediction"
-        ts_list = list(timesteps.tolist() if torch.is_tensor(timesteps) else timesteps)
-        if mode == "multistep":
-            coeffs = [sched.multistep_coeffs(i) for i in range(len(ts_list))]
-            hist = torch.empty_like(lat)  # first read on the first second-order step, after the step before has written it
-        else:
-            coeffs = [sched.step_coeffs(t, eta) for t in ts_list]
-        noise = predraw_step_noise(latents.shape, coeffs, generator, dev)
-        phi = guidance_rescale if do_cfg else 0.0  # the reference rescales only with CFG (:829)
-        k = 0
-        for i, (t, c) in enumerate(zip(ts_list, coeffs)):
-            ent["tb"].copy_(tb_table[i])
-            ent["graph"].replay()
-            z = None
-            if c.draws:
-                z = noise[k]
-                k += 1
-            if mode == "multistep":
-                ops.cfg_dpm_step_(ent["pred"], lat, hist, z, x_in, guidance_scale, phi, c, vpred)
-            else:
-                ops.cfg_sched_step_(ent["pred"], lat, z, x_in, guidance_scale, phi, c, vpred)
-            if callback is not None and i % callback_steps == 0:
-                callback(i, t, lat.permute(0, 3, 1, 2).contiguous())
-        return lat.permute(0, 3, 1, 2).contiguous()
+    def _conditioning(self, prompt_embeds, negative_prompt_embeds, do_cfg):
+        """-> (projected prompt embeddings, with CFG [negative, positive]; `added_cond_kwargs` of the UNet: none)."""
+        assert prompt_embeds is not None, "`prompt_embeds` must be provided by LLM."
+        prompt_embeds = self.projector(prompt_embeds.to(self.dtype))[-1]
+        if do_cfg:
+            assert negative_prompt_embeds is not None, \
+                "When using classifier free guidance, `negative_prompt_embeds` must be provided by LLM."
+            negative_prompt_embeds = self.projector(negative_prompt_embeds.to(self.dtype))[-1]
+            prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds])
+        return prompt_embeds, None
 
     @torch.no_grad()
     def pipeline(self, height: int | None = None, width: int | None = None, num_inference_steps: int = 50,
@@ -630,49 +504,12 @@ class StableDiffusionHead(MultimodalHead):
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(height, width, callback_steps, prompt_embeds, negative_prompt_embeds)
         batch_size = prompt_embeds.shape[0]
-        device = self.device
-        do_cfg = guidance_scale > 1.0
-        assert prompt_embeds is not None, "`prompt_embeds` must be provided by LLM."
-        prompt_embeds = self.projector(prompt_embeds.to(self.dtype))[-1]
-        if do_cfg:
-            assert negative_prompt_embeds is not None, \
-                "When using classifier free guidance, `negative_prompt_embeds` must be provided by LLM."
-            negative_prompt_embeds = self.projector(negative_prompt_embeds.to(self.dtype))[-1]
-            prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds])
+        prompt_embeds, added = self._conditioning(prompt_embeds, negative_prompt_embeds, guidance_scale > 1.0)
         sched = scheduler if scheduler is not None else self.noise_scheduler
-        sched.set_timesteps(num_inference_steps, device=device)
-        timesteps = sched.timesteps
+        sched.set_timesteps(num_inference_steps, device=self.device)
         latents = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.config.in_channels, height, width,
-                                       torch.float32, device, generator, latents)
-        mode = graph_denoise_mode(use_graph, sched, guidance_scale, guidance_rescale, eta, callback, num_images_per_prompt,
-                                  self.unet.config.in_channels)
-        if mode is not None:
-            latents = self._denoise_loop_graph(latents, prompt_embeds, timesteps.tolist(), sched, guidance_scale, mode=mode,
-                                               guidance_rescale=guidance_rescale, eta=eta, generator=generator, callback=callback,
-                                               callback_steps=callback_steps)
-        else:
-            ctx = self.unet.prepare_context(prompt_embeds)  # cross-attention K/V of the dream tokens: once, not per step
-            for i, t in enumerate(timesteps.tolist()):
-                model_in = torch.cat([latents] * 2) if do_cfg else latents
-                model_in = sched.scale_model_input(model_in, t)
-                noise_pred = self.unet(model_in.to(self.dtype), t, encoder_hidden_states=prompt_embeds, context_cache=ctx,
-                                       return_dict=False)[0].float()
-                if do_cfg:
-                    noise_pred_uncond, noise_pred_text = noise_pred.chunk(2)
-                    noise_pred = noise_pred_uncond + guidance_scale * (noise_pred_text - noise_pred_uncond)
-                    if guidance_rescale > 0.0:
-                        noise_pred = self._rescale_noise_cfg(noise_pred, noise_pred_text, guidance_rescale=guidance_rescale)
-                latents = sched.step(noise_pred, t, latents, eta=eta, generator=generator)
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, latents)
-        if output_type == "latent":
-            return latents
-        image = self.vae.decode((latents / self.vae.config.scaling_factor).to(self.dtype))
-        image = (image.float() / 2 + 0.5).clamp(0, 1)
-        if output_type == "pt":
-            return image
-        image = image.permute(0, 2, 3, 1).cpu().numpy()
-        if output_type == "np":
-            return image
-        import PIL.Image
-        return [PIL.Image.fromarray((im * 255).round().astype("uint8")) for im in image]
+                                       torch.float32, self.device, generator, latents)
+        latents = denoise(self, latents, prompt_embeds, sched, guidance_scale=guidance_scale, guidance_rescale=guidance_rescale,
+                          eta=eta, generator=generator, callback=callback, callback_steps=callback_steps,
+                          num_images_per_prompt=num_images_per_prompt, use_graph=use_graph, added_cond_kwargs=added)
+        return decode_output(self, latents, output_type)

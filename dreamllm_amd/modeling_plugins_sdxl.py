@@ -25,8 +25,8 @@ from typing import Any, Callable, Literal, Optional, Tuple
 
 import torch
 
-from . import ops
-from .modeling_plugins import StableDiffusionHead, graph_denoise_mode
+from .denoising import decode_output, denoise
+from .modeling_plugins import StableDiffusionHead
 from .projector import build_projector
 from .utils import logger
 
@@ -161,42 +161,16 @@ class StableDiffusionXLHead(StableDiffusionHead):
         global_states = self.global_projector(global_states)[-1]
         encoder_hidden_states = self.projector(encoder_hidden_states)[-1]
 
-        if self.noise_scheduler.config.prediction_type == "epsilon":
-            target = noise
-        elif self.noise_scheduler.config.prediction_type == "v_prediction":
-            target = self.noise_scheduler.get_velocity(latents, noise, timesteps)
-        else:
-            raise ValueError(f"Unknown prediction type {self.noise_scheduler.config.prediction_type}")
-
         added = {"time_ids": self._time_ids(add_time_ids, bsz, latents.device), "text_embeds": global_states}
         model_pred = self.unet(noisy_latents, timesteps, encoder_hidden_states, added_cond_kwargs=added).sample
-        if self.snr_gamma is None:
-            loss = ops.mse_loss(model_pred, target.float())
-        else:
-            snr = self._compute_snr(timesteps)
-            if self.noise_scheduler.config.prediction_type == "v_prediction":
-                snr = snr + 1
-            w = torch.stack([snr, self.snr_gamma * torch.ones_like(snr)], dim=1).min(dim=1)[0] / snr
-            loss = (ops.mse_loss_per_sample(model_pred, target.float()) * w).mean()
-        return loss
+        return self._diffusion_loss(model_pred, latents, noise, timesteps)
 
-    @torch.no_grad()
-    def pipeline(self, height: int | None = None, width: int | None = None, num_inference_steps: int = 100,
-                 guidance_scale: float = 7.5, num_images_per_prompt: int | None = 1, eta: float = 0.0, generator=None,
-                 latents=None, prompt_embeds=None, negative_prompt_embeds=None,
-                 output_type: Literal["latent", "pt", "np", "pil"] | None = "pil",
-                 callback: Callable[[int, int, torch.FloatTensor], None] | None = None, callback_steps: int = 1,
-                 cross_attention_kwargs: dict[str, Any] | None = None, guidance_rescale: float = 0.0,
-                 original_size: Optional[Tuple[int, int]] = None, crops_coords_top_left: Tuple[int, int] = (0, 0),
-                 target_size: Optional[Tuple[int, int]] = None, scheduler=None, use_graph: bool = True):
-        """dreamllm_sdxl/modeling_plugins.py:239-445."""
-        height = height or self.unet.config.sample_size * self.vae_scale_factor
-        width = width or self.unet.config.sample_size * self.vae_scale_factor
-        self.check_inputs(height, width, callback_steps, prompt_embeds, negative_prompt_embeds)
-        batch_size = prompt_embeds.shape[0]
-        device = self.device
-        do_cfg = guidance_scale > 1.0
+    def _conditioning(self, prompt_embeds, negative_prompt_embeds, do_cfg, original_size=None, crops_coords_top_left=(0, 0),
+                      target_size=None):
+        """The base head's, plus the UNet's `added_cond_kwargs`: the global projector on the mean over the dream queries
+        (`text_embeds`) and the micro-conditioning (`time_ids`), batch-doubled with CFG like the prompt embeddings (:333-378)."""
         assert prompt_embeds is not None, "`prompt_embeds` must be provided by LLM."
+        batch_size, device = prompt_embeds.shape[0], self.device
         prompt_embeds = prompt_embeds.to(self.dtype)
         global_prompt = self.global_projector(prompt_embeds.mean(1))[-1]
         prompt_embeds = self.projector(prompt_embeds)[-1]
@@ -217,41 +191,29 @@ class StableDiffusionXLHead(StableDiffusionHead):
             prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0)
             add_text_embeds = torch.cat([global_negative, global_prompt], dim=0)
             add_time_ids = torch.cat([add_time_ids, add_time_ids], dim=0)
+        return prompt_embeds, {"text_embeds": add_text_embeds, "time_ids": add_time_ids}
+
+    @torch.no_grad()
+    def pipeline(self, height: int | None = None, width: int | None = None, num_inference_steps: int = 100,
+                 guidance_scale: float = 7.5, num_images_per_prompt: int | None = 1, eta: float = 0.0, generator=None,
+                 latents=None, prompt_embeds=None, negative_prompt_embeds=None,
+                 output_type: Literal["latent", "pt", "np", "pil"] | None = "pil",
+                 callback: Callable[[int, int, torch.FloatTensor], None] | None = None, callback_steps: int = 1,
+                 cross_attention_kwargs: dict[str, Any] | None = None, guidance_rescale: float = 0.0,
+                 original_size: Optional[Tuple[int, int]] = None, crops_coords_top_left: Tuple[int, int] = (0, 0),
+                 target_size: Optional[Tuple[int, int]] = None, scheduler=None, use_graph: bool = True):
+        """dreamllm_sdxl/modeling_plugins.py:239-445."""
+        height = height or self.unet.config.sample_size * self.vae_scale_factor
+        width = width or self.unet.config.sample_size * self.vae_scale_factor
+        self.check_inputs(height, width, callback_steps, prompt_embeds, negative_prompt_embeds)
+        batch_size = prompt_embeds.shape[0]
+        prompt_embeds, added = self._conditioning(prompt_embeds, negative_prompt_embeds, guidance_scale > 1.0, original_size,
+                                                  crops_coords_top_left, target_size)
         sched = scheduler if scheduler is not None else self.noise_scheduler
-        sched.set_timesteps(num_inference_steps, device=device)
-        timesteps = sched.timesteps
+        sched.set_timesteps(num_inference_steps, device=self.device)
         latents = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.config.in_channels, height, width,
-                                       torch.float32, device, generator, latents)
-        added = {"text_embeds": add_text_embeds, "time_ids": add_time_ids}
-        mode = graph_denoise_mode(use_graph, sched, guidance_scale, guidance_rescale, eta, callback, num_images_per_prompt,
-                                  self.unet.config.in_channels)
-        if mode is not None:
-            latents = self._denoise_loop_graph(latents, prompt_embeds, timesteps.tolist(), sched, guidance_scale,
-                                               added_cond_kwargs=added, mode=mode, guidance_rescale=guidance_rescale, eta=eta,
-                                               generator=generator, callback=callback, callback_steps=callback_steps)
-        else:
-            ctx = self.unet.prepare_context(prompt_embeds)
-            for i, t in enumerate(timesteps.tolist()):
-                model_in = torch.cat([latents] * 2) if do_cfg else latents
-                model_in = sched.scale_model_input(model_in, t)
-                noise_pred = self.unet(model_in.to(self.dtype), t, encoder_hidden_states=prompt_embeds, context_cache=ctx,
-                                       added_cond_kwargs=added, return_dict=False)[0].float()
-                if do_cfg:
-                    noise_pred_uncond, noise_pred_text = noise_pred.chunk(2)
-                    noise_pred = noise_pred_uncond + guidance_scale * (noise_pred_text - noise_pred_uncond)
-                    if guidance_rescale > 0.0:
-                        noise_pred = self._rescale_noise_cfg(noise_pred, noise_pred_text, guidance_rescale=guidance_rescale)
-                latents = sched.step(noise_pred, t, latents, eta=eta, generator=generator)
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, latents)
-        if output_type == "latent":
-            return latents
-        image = self.vae.decode((latents / self.vae.config.scaling_factor).to(self.dtype))
-        image = (image.float() / 2 + 0.5).clamp(0, 1)
-        if output_type == "pt":
-            return image
-        image = image.permute(0, 2, 3, 1).cpu().numpy()
-        if output_type == "np":
-            return image
-        import PIL.Image
-        return [PIL.Image.fromarray((im * 255).round().astype("uint8")) for im in image]
+                                       torch.float32, self.device, generator, latents)
+        latents = denoise(self, latents, prompt_embeds, sched, guidance_scale=guidance_scale, guidance_rescale=guidance_rescale,
+                          eta=eta, generator=generator, callback=callback, callback_steps=callback_steps,
+                          num_images_per_prompt=num_images_per_prompt, use_graph=use_graph, added_cond_kwargs=added)
+        return decode_output(self, latents, output_type)

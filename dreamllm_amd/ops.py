@@ -1657,22 +1657,31 @@ def cfg_ddim_step_(pred, latents, next_in, guidance, a_t, a_prev, v_prediction=F
     return latents
 
 
+def _cfg_step_operands(fn, pred, latents, next_in, like_latents):
+    """The operand checks `cfg_sched_step_` and `cfg_dpm_step_` share -> (B, P, G).  `like_latents`: (name, tensor, required)
+    triples of operands that are fp32 contiguous of the latents' shape."""
+    B, P = latents.shape[0], latents.numel() // (4 * max(latents.shape[0], 1))
+    if pred.dtype != torch.bfloat16 or latents.dtype != torch.float32 or latents.shape[-1] != 4 or not latents.is_contiguous():
+        raise ValueError(f"{fn}: pred bf16 [G*B,...,4], latents fp32 contiguous [B,...,4]")
+    G = pred.numel() // max(latents.numel(), 1)
+    if pred.numel() != G * latents.numel() or not pred.is_contiguous():
+        raise ValueError(f"{fn}: pred {tuple(pred.shape)} is not G x latents {tuple(latents.shape)}")
+    for name, t, required in like_latents:
+        if (t is None and required) or (t is not None and (t.dtype != torch.float32 or t.shape != latents.shape
+                                                           or not t.is_contiguous())):
+            raise ValueError(f"{fn}: {name} must be fp32 contiguous like latents")
+    if next_in is not None and (next_in.dtype != torch.bfloat16 or next_in.numel() != 2 * G * latents.numel()
+                                or not next_in.is_contiguous()):
+        raise ValueError(f"{fn}: next_in must be bf16 contiguous [G*B,...,8]")
+    return B, P, G
+
+
 def cfg_sched_step_(pred, latents, noise, next_in, guidance, rescale, coeffs, v_prediction=False):
     """Fused CFG combine (+ guidance rescale) + scheduler step from `coeffs` (schedulers.StepCoeffs) + next UNet input, in place
     on the fp32 NHWC latents [B,H,W,4].  pred bf16 [G*B,H,W,4] (G = 2 with CFG, uncond first; G = 1 without), noise fp32 like
     latents (used when coeffs.sigma != 0) or None, next_in bf16 [G*B,H,W,8] or None."""
     _need_gpu(pred, latents, noise, next_in)
-    B, P = latents.shape[0], latents.numel() // (4 * max(latents.shape[0], 1))
-    if pred.dtype != torch.bfloat16 or latents.dtype != torch.float32 or latents.shape[-1] != 4 or not latents.is_contiguous():
-        raise ValueError("cfg_sched_step_: pred bf16 [G*B,...,4], latents fp32 contiguous [B,...,4]")
-    G = pred.numel() // max(latents.numel(), 1)
-    if pred.numel() != G * latents.numel() or not pred.is_contiguous():
-        raise ValueError(f"cfg_sched_step_: pred {tuple(pred.shape)} is not G x latents {tuple(latents.shape)}")
-    if noise is not None and (noise.dtype != torch.float32 or noise.shape != latents.shape or not noise.is_contiguous()):
-        raise ValueError("cfg_sched_step_: noise must be fp32 contiguous like latents")
-    if next_in is not None and (next_in.dtype != torch.bfloat16 or next_in.numel() != 2 * G * latents.numel()
-                                or not next_in.is_contiguous()):
-        raise ValueError("cfg_sched_step_: next_in must be bf16 contiguous [G*B,...,8]")
+    B, P, G = _cfg_step_operands("cfg_sched_step_", pred, latents, next_in, [("noise", noise, False)])
     c = coeffs
     check("dllm_cfg_sched_step", _p(pred), _p(latents), _p(noise), _p(next_in), B, P, G, float(guidance), float(rescale),
           int(v_prediction), c.sqrt_at, c.sqrt_1mat, c.k_x0, c.k_eps, c.k_x, c.sigma, _stream())
@@ -1684,19 +1693,7 @@ def cfg_dpm_step_(pred, latents, hist, noise, next_in, guidance, rescale, coeffs
     input, in place on the fp32 NHWC latents [B,H,W,4].  hist fp32 like latents: the data prediction of the step before (read only
     when coeffs.k_m1 != 0), overwritten with this step's.  pred, noise and next_in as in `cfg_sched_step_`."""
     _need_gpu(pred, latents, hist, noise, next_in)
-    B, P = latents.shape[0], latents.numel() // (4 * max(latents.shape[0], 1))
-    if pred.dtype != torch.bfloat16 or latents.dtype != torch.float32 or latents.shape[-1] != 4 or not latents.is_contiguous():
-        raise ValueError("cfg_dpm_step_: pred bf16 [G*B,...,4], latents fp32 contiguous [B,...,4]")
-    G = pred.numel() // max(latents.numel(), 1)
-    if pred.numel() != G * latents.numel() or not pred.is_contiguous():
-        raise ValueError(f"cfg_dpm_step_: pred {tuple(pred.shape)} is not G x latents {tuple(latents.shape)}")
-    if hist is None or hist.dtype != torch.float32 or hist.shape != latents.shape or not hist.is_contiguous():
-        raise ValueError("cfg_dpm_step_: hist must be fp32 contiguous like latents")
-    if noise is not None and (noise.dtype != torch.float32 or noise.shape != latents.shape or not noise.is_contiguous()):
-        raise ValueError("cfg_dpm_step_: noise must be fp32 contiguous like latents")
-    if next_in is not None and (next_in.dtype != torch.bfloat16 or next_in.numel() != 2 * G * latents.numel()
-                                or not next_in.is_contiguous()):
-        raise ValueError("cfg_dpm_step_: next_in must be bf16 contiguous [G*B,...,8]")
+    B, P, G = _cfg_step_operands("cfg_dpm_step_", pred, latents, next_in, [("hist", hist, True), ("noise", noise, False)])
     c = coeffs
     check("dllm_cfg_dpm_step", _p(pred), _p(latents), _p(hist), _p(noise), _p(next_in), B, P, G, float(guidance), float(rescale),
           int(v_prediction), c.sqrt_at, c.sqrt_1mat, c.k_x, c.k_m0, c.k_m1, c.sigma, _stream())
