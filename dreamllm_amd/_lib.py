@@ -43,6 +43,8 @@ SIGNATURES = {
     "dllm_cfg_dpm_step": [c_void_p] * 5 + [c_i64, c_i64, c_int, c_float, c_float, c_int] + [c_float] * 6 + [c_void_p],
     "dllm_gemv_bf16": [c_void_p] * 4 + [c_int] + [c_i64] * 6 + [c_int, c_void_p],
     "dllm_gemv_fused": [c_void_p, c_void_p, c_float] + [c_void_p] * 7 + [c_int] + [c_i64] * 10 + [c_int, c_int, c_void_p],
+    "dllm_gemv_w8": [c_void_p] * 5 + [c_int] + [c_i64] * 6 + [c_int, c_void_p],
+    "dllm_gemv_fused_w8": [c_void_p, c_void_p, c_float] + [c_void_p] * 10 + [c_int] + [c_i64] * 10 + [c_int, c_int, c_void_p],
     "dllm_rope_append": [c_void_p] * 9 + [c_int] * 4 + [c_i64] * 5 + [c_void_p],
     "dllm_attn_decode": [c_void_p] * 6 + [c_i64] + [c_void_p] * 2 + [c_int] * 4 + [c_i64] * 7 + [c_float, c_int, c_void_p],
     "dllm_attn_decode_rope": [c_void_p] * 11 + [c_i64] + [c_void_p] * 3 + [c_int] * 4 + [c_i64] * 8 + [c_float, c_int, c_void_p],

@@ -16,6 +16,10 @@ kernels and launchers stay in `ops` with their unit tests, the session no longer
 
 The step is captured once per (batch, max_len) in a hipGraph (`torch.cuda.CUDAGraph`) and replayed per token; nothing in it depends
 on the host.  Prefill runs through the normal model forward (MFMA GEMMs + flash attention) and its K/V are copied into the cache.
+
+Opt-in FP8 weight-only decoding (`weights=DecodeWeightsFP8.from_model(model)`, `model.quantize_decode_weights`): the four GEMV launches
+of a layer read e4m3 copies of the decoder weights (csrc/gemv_w8.hip) -- half the bytes of the stream that bounds the step.  The
+prefill, the embedding, the norms and lm_head stay bf16: the prompt is encoded with W, the new tokens with Q(W).
 """
 from __future__ import annotations
 
@@ -27,15 +31,54 @@ from . import ops
 from .generation import check_left_padded, left_pad_position_ids, phase_seed
 
 
+class DecodeWeightsFP8:
+    """FP8 (OCP e4m3fn) copies of the decoder's Linear weights for the token step: `ops.quantize_rows_e4m3` of every q/k/v/o and
+    gate/up/down projection, one fp32 scale per output row.  `layers[i]` holds `qkv` / `qkv_scale` (the q|k|v rows packed into one
+    matrix with one scale vector; `qkv_parts` / `qkv_scale_parts` are the three matrices as views of them) and `o`, `gate`, `up`,
+    `down` with their `*_scale`.  The embedding, the norms and `lm_head` are not quantised: a session reads them from the model.
+
+    A plain holder and a SNAPSHOT: it does not follow later changes of the model's weights; build it again after they change."""
+
+    def __init__(self, layers):
+        self.layers = layers
+
+    @classmethod
+    @torch.no_grad()
+    def from_model(cls, model):
+        layers = []
+        for layer in model.model.layers:
+            at, mlp = layer.self_attn, layer.mlp
+            qkv = [ops.quantize_rows_e4m3(p.weight.detach()) for p in (at.q_proj, at.k_proj, at.v_proj)]
+            rows = [q.shape[0] for q, _ in qkv]
+            # packed as bytes: torch.cat has no float8 kernel on every build
+            e = {"qkv": torch.cat([q.view(torch.uint8) for q, _ in qkv]).view(torch.float8_e4m3fn),
+                 "qkv_scale": torch.cat([s for _, s in qkv])}
+            e["qkv_parts"], e["qkv_scale_parts"] = e["qkv"].split(rows), e["qkv_scale"].split(rows)
+            for name, lin in (("o", at.o_proj), ("gate", mlp.gate_proj), ("up", mlp.up_proj), ("down", mlp.down_proj)):
+                e[name], e[name + "_scale"] = ops.quantize_rows_e4m3(lin.weight.detach())
+            layers.append(e)
+        return cls(layers)
+
+    def nbytes(self):
+        """Device bytes of the codes and scales."""
+        return sum(t.numel() * t.element_size() for e in self.layers for t in e.values() if isinstance(t, torch.Tensor))
+
+
 class GreedyDecodeSession:
     def __init__(self, model, batch_size: int, max_len: int, use_graph: bool = True, nsplit: int = 8, fused: bool = True,
-                 vocab_limit: int | None = 32000):
+                 vocab_limit: int | None = 32000, weights: DecodeWeightsFP8 | None = None):
         """`vocab_limit`: argmax runs over `logits[..., :vocab_limit]` -- the reference loop slices `[..., :32000]`
         (omni/eval/language_eval/modeling_dreamllm.py:79,86) so that none of the added special tokens (<dream_start>, <im_*>,
         [PAD] ...) can be emitted; None = whole vocabulary.  `fused=False`: the token step one launch per operation, the
-        reference form of the fused step in the tests."""
+        reference form of the fused step in the tests.
+
+        `weights`: a `DecodeWeightsFP8` -- the token step then streams the FP8 copies of the decoder's Linear weights (`ops.gemv_w8`
+        / `ops.gemv_fused_w8`, the same launches in the same places, so graph capture is unchanged).  The embedding, the norms and
+        `lm_head` stay bf16, and the PREFILL stays on the bf16 model forward: the prompt is encoded with W, the new tokens with
+        Q(W)."""
         cfg = model.config
         self.model = model
+        self.weights = weights
         self.B, self.max_len, self.use_graph, self.nsplit, self.fused = batch_size, max_len, use_graph, nsplit, fused
         if batch_size > 8:
             raise ValueError("the decode GEMV handles up to 8 sequences per step")
@@ -71,7 +114,10 @@ class GreedyDecodeSession:
         eps = cfg.rms_norm_eps
         x = m.model.embed_tokens.weight.index_select(0, self.tok)  # [B, d]
         pos = self.pos.view(-1)
-        for li, layer in enumerate(m.model.layers):
+        layers = m.model.layers
+        if self.weights is not None:  # FP8 copies of the decoder's Linear weights: the same launches over ops.gemv*_w8
+            x, layers = self._layers_w8(x, pos), ()
+        for li, layer in enumerate(layers):
             at, mlp = layer.self_attn, layer.mlp
             if self.fused:
                 # 6 launches per layer: [RMSNorm + q/k/v GEMV] [RoPE + cache append + attention x2] [o GEMV + residual]
@@ -109,6 +155,40 @@ class GreedyDecodeSession:
         self._choose(logits)
         self._advance()
         return logits
+
+    def _layers_w8(self, x, pos):
+        """The decoder layers of `_token_step` over `self.weights` (FP8 codes + per-row scales): launch for launch the bf16 loop, in
+        the fused and in the one-launch-per-operation form."""
+        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
+        eps = self.model.config.rms_norm_eps
+        scale = 1.0 / math.sqrt(D)
+        for li, (layer, w) in enumerate(zip(self.model.model.layers, self.weights.layers)):
+            qkv, qs = w["qkv_parts"], w["qkv_scale_parts"]
+            if self.fused:
+                q, k, v = ops.gemv_fused_w8(x, qkv, qs, norm_w=layer.input_layernorm.weight, eps=eps)
+                o = ops.attn_decode_rope(q.view(B, H, D), k.view(B, Hkv, D), v.view(B, Hkv, D), self.kc[li], self.vc[li], self.kv_len,
+                                         self.cos, self.sin, pos, scale, self.nsplit, kv_start=self.kv_start, row_map=self.row_map)
+                x2 = ops.gemv_w8(o.view(B, H * D), w["o"], w["o_scale"], residual=x)
+                act = ops.gemv_fused_w8(x2, (w["gate"], w["up"]), (w["gate_scale"], w["up_scale"]),
+                                        norm_w=layer.post_attention_layernorm.weight, eps=eps, swiglu=True)
+                x = ops.gemv_w8(act, w["down"], w["down_scale"], residual=x2)
+                continue
+            h, _, _ = ops.rmsnorm_fwd(x, layer.input_layernorm.weight, eps)
+            q = ops.gemv_w8(h, qkv[0], qs[0]).view(B, 1, H, D)
+            k = ops.gemv_w8(h, qkv[1], qs[1]).view(B, 1, Hkv, D)
+            v = ops.gemv_w8(h, qkv[2], qs[2])
+            ops.rope_(q, self.cos, self.sin, self.pos)
+            ops.rope_(k, self.cos, self.sin, self.pos)
+            self.kc[li].view(B * self.max_len, Hkv * D).index_copy_(0, self.slot, k.view(B, Hkv * D))
+            self.vc[li].view(B * self.max_len, Hkv * D).index_copy_(0, self.slot, v)
+            o = ops.attn_decode(q.view(B, H, D), self.kc[li], self.vc[li], self.kv_len, scale, self.nsplit,
+                                kv_start=self.kv_start, row_map=self.row_map)
+            x2 = ops.gemv_w8(o.view(B, H * D), w["o"], w["o_scale"], residual=x)
+            h2, _, _ = ops.rmsnorm_fwd(x2, layer.post_attention_layernorm.weight, eps)
+            g = ops.gemv_w8(h2, w["gate"], w["gate_scale"])
+            u = ops.gemv_w8(h2, w["up"], w["up_scale"])
+            x = ops.gemv_w8(ops.glu_fwd(g, u, 0), w["down"], w["down_scale"], residual=x2)
+        return x
 
     def _advance(self):
         """End of a token step (inside the captured graph): every row moves on to its next position and cache slot."""

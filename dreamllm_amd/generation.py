@@ -115,9 +115,19 @@ class ModelStepper:
         return self.logits
 
 
+def decode_weights(model):
+    """The FP8 decode-weight holder set by `model.quantize_decode_weights` (`decode.DecodeWeightsFP8`), or None: what every fast
+    path passes to its session as `weights=`."""
+    return getattr(model, "_decode_weights", None)
+
+
 def cached_session(model, key, factory):
     """The model's one decode session (`model._decode_session = (key, session)`, assignable to None to drop it): equal calls reuse
-    it and its captured graph, a call of another kind or shape replaces it.  `key`: a tuple starting with the session kind."""
+    it and its captured graph, a call of another kind or shape replaces it.  `key`: a tuple starting with the session kind; a
+    decode-weight holder on the model is made part of it here, so setting or dropping the holder replaces the session too."""
+    held_weights = decode_weights(model)
+    if held_weights is not None:
+        key = key + (("weights", held_weights),)
     held = getattr(model, "_decode_session", None)
     if held is None or held[0] != key:
         held = (key, factory())
@@ -160,7 +170,8 @@ def greedy_decode(model, input_ids, max_new_tokens, images=None, fast=None, use_
         from .decode import GreedyDecodeSession
         max_len = prompt.shape[1] + n_new + 1
         sess = cached_session(model, ("greedy", B, max_len, use_graph, V),
-                              lambda: GreedyDecodeSession(model, B, max_len, use_graph=use_graph, vocab_limit=V))
+                              lambda: GreedyDecodeSession(model, B, max_len, use_graph=use_graph, vocab_limit=V,
+                                                          weights=decode_weights(model)))
         first = sess.prefill(prompt, images=images, attention_mask=attention_mask, forced_tokens=forced, forced_mask=fm)
         new = torch.cat([first[:, None], sess.generate(n_new - 1)], dim=1)
     else:
@@ -198,7 +209,7 @@ def sampled_decode(model, input_ids, max_new_tokens, temperature, top_k, top_p, 
         sess = cached_session(
             model, ("sample", B, max_len, use_graph, V, temperature, top_k, top_p, eos, int(pad), greedy),
             lambda: SampledDecodeSession(model, B, max_len, temperature, top_k, top_p, eos=eos, pad=pad, use_graph=use_graph,
-                                         vocab_limit=V, fixed_u=0.0 if greedy else None))
+                                         vocab_limit=V, fixed_u=0.0 if greedy else None, weights=decode_weights(model)))
         first = sess.prefill(prompt, images=images, attention_mask=attention_mask, forced_tokens=forced, forced_mask=fm, seed=seed)
         parts, all_finished = [first[:, None]], False
 
@@ -271,7 +282,8 @@ def beam_decode(model, input_ids, max_new_tokens, nb, nrs, length_penalty, early
         sess = cached_session(
             model, ("beam", B, nb, max_length + 1, use_graph, eos, pad, length_penalty, early_stopping, max_new_tokens),
             lambda: BeamDecodeSession(model, B, nb, max_length + 1, eos=eos, pad=pad, length_penalty=length_penalty,
-                                      early_stopping=early_stopping, max_new=max_new_tokens, use_graph=use_graph))
+                                      early_stopping=early_stopping, max_new=max_new_tokens, use_graph=use_graph,
+                                      weights=decode_weights(model)))
         sess.prefill(input_ids, images=images, attention_mask=attention_mask)
         state = sess.beam
         n = run_chunked(sess, max_new_tokens, bool(crit), lambda n, chunk: criteria_stop(state, n - 1) or bool(state.done.all()))
@@ -488,7 +500,7 @@ def interleaved_decode(model, input_ids, max_new_tokens, max_images, temperature
     sess = cached_session(
         model, ("interleave", B, max_len, use_graph, temperature, top_k, top_p, eos, int(pad), greedy, layout.trigger),
         lambda: InterleavedDecodeSession(model, B, max_len, temperature, top_k, top_p, eos=eos, pad=pad, trigger=layout.trigger,
-                                         use_graph=use_graph, fixed_u=0.0 if greedy else None))
+                                         use_graph=use_graph, fixed_u=0.0 if greedy else None, weights=decode_weights(model)))
     cnt, n_img = [0] * B, [0] * B                # new tokens so far (layout included), images so far
     cur, pos = [S] * B, list(plen)               # cache slot and position id of the row's first token of the phase
     start = [S - n for n in plen]

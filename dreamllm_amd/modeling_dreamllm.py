@@ -1250,6 +1250,31 @@ class DreamLLMForCausalMLM(DreamLLMPreTrainedModel):
                              "images": kwargs.get("images", None)})
         return model_inputs
 
+    DECODE_WEIGHT_FORMATS = ("fp8_e4m3",)
+
+    @torch.no_grad()
+    def quantize_decode_weights(self, fmt="fp8_e4m3"):
+        """Opt in to FP8 weight-only decoding (INTEGRATION.md "FP8 weight-only decoding"): `"fp8_e4m3"` builds a
+        `decode.DecodeWeightsFP8` (OCP e4m3fn codes + one fp32 scale per output row of every decoder q/k/v/o/gate/up/down weight) and
+        stores it; `None` drops it; any other format raises ValueError.  Returns the holder (or None).
+
+        While it is set, every FAST path -- `greedy_generate`, `sample_generate`, `generate` (greedy, sampling, beams),
+        `generate_interleaved` -- runs its token steps over the FP8 copies (half the weight bytes per token); the cached decode
+        session is replaced when the holder is set or dropped.  What stays bf16: the embedding, the norms, `lm_head` (the logits are
+        not quantised) and the PREFILL, which is the bf16 model forward -- the prompt is encoded with W, the new tokens with Q(W).
+        `fast=False` ignores the holder.  Both copies of the weights stay on the device (about +6.5 GB at 7B).
+
+        The holder is a SNAPSHOT of the weights at the time of the call: after they change (training, `load_state_dict`), call this
+        again."""
+        if fmt is None:
+            self._decode_weights = None
+            return None
+        if fmt not in self.DECODE_WEIGHT_FORMATS:
+            raise ValueError(f"quantize_decode_weights: unknown format {fmt!r} (supported: {self.DECODE_WEIGHT_FORMATS}, or None)")
+        from .decode import DecodeWeightsFP8
+        self._decode_weights = DecodeWeightsFP8.from_model(self)
+        return self._decode_weights
+
     @torch.no_grad()
     def greedy_generate(self, input_ids, max_new_tokens, images=None, fast=None, use_graph=True, attention_mask=None,
                         pad_token_id=None, vocab_limit="auto"):

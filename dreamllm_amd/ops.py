@@ -2283,6 +2283,103 @@ def gemv_fused(x, weights, norm_w=None, eps=0.0, residual=None, swiglu=False, ou
     return outs[0] if swiglu else outs
 
 
+# ----------------------------------------------------------------------------------- FP8 weight-only decode (csrc/gemv_w8.hip)
+E4M3_MAX = 448.0
+
+
+def quantize_rows_e4m3(w):
+    """bf16 weight [N, K] -> (q `torch.float8_e4m3fn` [N, K], scale fp32 [N]): OCP e4m3fn (not fnuz), symmetric, one scale per output
+    row, w ~ scale[:, None] * q.  scale = amax / 448 (1 for an all-zero row); the codes saturate at +-448 (torch's cast alone would
+    turn 500 into NaN).  Plain torch ops on the weight's device: this runs once per model, not per token."""
+    if not isinstance(w, torch.Tensor) or w.dim() != 2:
+        raise ValueError("quantize_rows_e4m3: a 2-D weight [N, K]")
+    _bf16(w)
+    wf = w.float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_rows_e4m3: the weight has non-finite entries")
+    amax = wf.abs().amax(1)
+    # tensor / tensor on purpose: with a Python scalar on either side torch may multiply by a reciprocal on the device, one ulp away
+    # from the division the CPU does
+    one = torch.ones_like(amax)
+    scale = torch.where(amax > 0, amax / torch.full_like(amax, E4M3_MAX), one)
+    inv = one / scale
+    q = (wf * inv[:, None]).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    return q, scale
+
+
+def _w8_operand(q, scale, K, name):
+    if q.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"{name}: expected float8_e4m3fn codes, got {q.dtype}")
+    if scale.dtype != torch.float32:
+        raise TypeError(f"{name}: expected fp32 scales, got {scale.dtype}")
+    if q.dim() != 2 or q.shape[1] != K or scale.shape != (q.shape[0],):
+        raise ValueError(f"{name}: codes [N, K] sharing K with x and one scale per row")
+    return (q if q.is_contiguous() else q.contiguous()), (scale if scale.is_contiguous() else scale.contiguous())
+
+
+def _w8_x(x, name):
+    x2 = x.reshape(-1, x.shape[-1])
+    if x2.stride(-1) != 1:
+        x2 = x2.contiguous()
+    M, K = x2.shape
+    if K % 16:
+        raise ValueError(f"{name}: K must be a multiple of 16 (a lane owns 16 codes), got {K}")
+    if M > 8:
+        raise ValueError(f"{name}: at most 8 rows of x, got {M}")
+    return x2, M, K
+
+
+def gemv_w8(x, q, scale, residual=None, out_dtype=torch.bfloat16, out=None):
+    """`gemv` over an FP8 weight (`quantize_rows_e4m3`): y[M,N] = scale[n] * (x[M,K] q[N,K]^T) (+ residual), M <= 8, K % 16 == 0."""
+    _need_gpu(x, q, scale, residual)
+    _bf16(x, residual)
+    x2, M, K = _w8_x(x, "gemv_w8")
+    qc, sc = _w8_operand(q, scale, K, "gemv_w8")
+    N = qc.shape[0]
+    r2 = None
+    if residual is not None:
+        r2 = residual.reshape(-1, N)
+        if r2.stride(-1) != 1:
+            r2 = r2.contiguous()
+    if out is None:
+        out = torch.empty(M, N, dtype=out_dtype, device=x.device)
+    check("dllm_gemv_w8", _p(x2), _p(qc), _p(sc), _p(out), _p(r2), M, N, K, x2.stride(0), K, out.stride(0),
+          r2.stride(0) if r2 is not None else 0, _dt(out), _stream())
+    return out
+
+
+def gemv_fused_w8(x, weights, scales, norm_w=None, eps=0.0, residual=None, swiglu=False, out_dtype=torch.bfloat16):
+    """`gemv_fused` over FP8 weights: `weights` 1..3 code matrices sharing K, `scales` their per-row scale vectors; the folded
+    RMSNorm, the q|k|v packing, the residual and the SwiGLU pair as in the bf16 form."""
+    _need_gpu(x, norm_w, residual, *weights, *scales)
+    _bf16(x, norm_w, residual)
+    x2, M, K = _w8_x(x, "gemv_fused_w8")
+    if not 1 <= len(weights) <= 3 or len(scales) != len(weights):
+        raise ValueError("gemv_fused_w8: 1..3 weight matrices with a common K, one scale vector each")
+    ws, ss = zip(*[_w8_operand(w, s, K, "gemv_fused_w8") for w, s in zip(weights, scales)])
+    Ns = [w.shape[0] for w in ws]
+    if swiglu:
+        if len(ws) != 2 or Ns[0] != Ns[1]:
+            raise ValueError("gemv_fused_w8(swiglu): weights = (gate, up) of equal shape")
+        outs = [torch.empty(M, Ns[0], dtype=torch.bfloat16, device=x.device)]
+    else:
+        outs = [torch.empty(M, n, dtype=out_dtype, device=x.device) for n in Ns]
+    r2 = None
+    if residual is not None:
+        r2 = residual.reshape(-1, Ns[0])
+        if r2.stride(-1) != 1:
+            r2 = r2.contiguous()
+    wp = [_p(w) for w in ws] + [None] * (3 - len(ws))
+    sp = [_p(s) for s in ss] + [None] * (3 - len(ss))
+    yp = [_p(o) for o in outs] + [None] * (3 - len(outs))
+    nn_ = Ns + [0] * (3 - len(Ns))
+    ldy = [o.stride(0) for o in outs] + [0] * (3 - len(outs))
+    check("dllm_gemv_fused_w8", _p(x2), _p(norm_w), float(eps), wp[0], wp[1], wp[2], sp[0], sp[1], sp[2], yp[0], yp[1], yp[2], _p(r2),
+          M, nn_[0], nn_[1], nn_[2], K, x2.stride(0), K, ldy[0], ldy[1], ldy[2], r2.stride(0) if r2 is not None else 0,
+          int(swiglu), _dt(outs[0]), _stream())
+    return outs[0] if swiglu else outs
+
+
 def rope_append_(q, k, v, kcache, vcache, cos, sin, pos, kv_len=None):
     """q [B,H,D] rotated in place with rotary position pos[b]; k [B,Hkv,D] rotated into kcache[b, slot]; v copied into
     vcache[b, slot]; slot = kv_len[b] - 1 (int32 [B] on device) or pos[b] when kv_len is None (pos: int64 [B] on device).

@@ -294,6 +294,18 @@ int dllm_gemv_fused(const void* x, const void* norm_w, float eps, const void* W0
 int dllm_rope_append(void* q, const void* k, const void* v, void* kcache, void* vcache, const float* cos_tab, const float* sin_tab,
                      const int64_t* pos, const int* kv_len, int B, int H, int Hkv, int D, int64_t q_sb, int64_t kv_sb, int64_t c_sb,
                      int64_t c_ss, int64_t c_sh, void* stream);
+/* FP8 weight-only twins of the two GEMVs above (csrc/gemv_w8.hip): the weight is OCP e4m3fn codes [N][ldw] (one byte per element,
+ * ldw in bytes, a multiple of 16) with one fp32 scale per output row; x, norm_w, residual and the bf16 outputs as above.
+ * y[m][n] = round(scale[n] * sum_k q[n][k] h[m][k] (+ residual[m][n])): fp32 accumulation of exact products, the scale applied once
+ * to the reduced sum.  M <= 8 and K % 16 == 0, else DLLM_ERR_SHAPE (also for a null x / weight / scale / y).  M <= 4 with
+ * M * roundup(K, 1024) * 2 <= 60 KiB stages x in LDS, every other shape reads it through L1; both forms, and the plain and the fused
+ * entry point, accumulate in one order (fused == unfused chain, bit for bit). */
+int dllm_gemv_w8(const void* x, const void* Wq, const float* scale, void* y, const void* residual, int M, int64_t N, int64_t K,
+                 int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, int out_dtype, void* stream);
+int dllm_gemv_fused_w8(const void* x, const void* norm_w, float eps, const void* W0, const void* W1, const void* W2, const float* s0,
+                       const float* s1, const float* s2, void* y0, void* y1, void* y2, const void* residual, int M, int64_t N0,
+                       int64_t N1, int64_t N2, int64_t K, int64_t ldx, int64_t ldw, int64_t ldy0, int64_t ldy1, int64_t ldy2,
+                       int64_t ldr, int swiglu, int out_dtype, void* stream);
 /* Sampled token choice of a decode step (csrc/sample.hip; omni/eval/language_eval/modeling_dreamllm.py:36-43,86-91 `sample_top_p`,
  * omni/eval/vqa/vqa_inference.py:111-137 `generate(do_sample=True)` = transformers 4.35.2 [ext] temperature -> top-k -> top-p ->
  * multinomial).  One block per row of fp32 logits [B][ld], V <= 32768 ids considered (ids >= V are never emitted):
